@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: exact top-5 MIPS queries/second (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and no more: build the index, warm up, time the K steps (`value`,
+`ms_per_step`, and `roofline` from the scan kernel's HIP events inside those steps), check the last step's results,
+write them if --dump-outputs is given, print the line.  --full adds everything that takes runs of its own: the
+per-step event pass (`step_ms`), the CPU baselines with their parity check, and the extra `regimes` below.
+--dump-outputs DIR writes the last timed step's top-k as DIR/scores.npy (float32) and DIR/indices.npy (row ids as
+float64, exact): the inputs are seeded, so two builds can be compared output for output.
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks ITSELF (a child
 `python -m torch.distributed.run ...` of this same file, spawned before this process touches the GPU), relays
@@ -68,7 +75,25 @@ def parse():
                     help="gloo = rehearsal of the N > 1 path on ONE GPU (all ranks on cuda:0, host-staged collective)")
     ap.add_argument("--launch-check", action="store_true",
                     help="form the N-rank process group, exchange one tensor, print what was formed and exit (no search, no GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-step event times, CPU baselines + parity, extra regimes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's top-k (scores.npy float32, indices.npy float64) into DIR")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+def dump_outputs(out_dir, s, i):
+    """--dump-outputs: what a caller of the timed search receives from its last step -- the top-k scores and row ids of
+    every query (ids as float64: exact below 2^53; IDX_POISON / -1 keep their values)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    s = s.cpu().numpy()
+    np.save(os.path.join(out_dir, "scores.npy"), s if s.dtype in (np.float32, np.float64) else s.astype(np.float32))
+    np.save(os.path.join(out_dir, "indices.npy"), i.cpu().numpy().astype(np.float64))
 
 
 def self_launch(args) -> int:
@@ -449,11 +474,13 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1e3
     value = nq * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, s, i)
 
-    # a second, untimed-for-`value` pass with one event pair per step: the distribution of step times
+    # --full: a second, untimed-for-`value` pass with one event pair per step: the distribution of step times
     # (median and min).  Un-pipelined, so each sample is one complete step.
     step_ms = []
-    if world == 1 or not pipelined:
+    if args.full and (world == 1 or not pipelined):
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
         for a, b in evs:
             a.record()
@@ -513,7 +540,7 @@ def main():
 
     cpu = cpu_t = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import numpy as np
 
         cpu, cpu_t, (cs, ci), (ts, ti) = cpu_baselines(index.local, q_dev, args)
@@ -524,7 +551,7 @@ def main():
                   "max_rel_score_diff_torch": float(np.max(np.abs(gs[: ts.shape[0]] - ts) / np.abs(ts)))}
 
     regimes = None
-    if rank == 0 and world == 1 and not args.no_regimes and not f8 and (n, d) == (1 << 20, 768):
+    if args.full and rank == 0 and world == 1 and not args.no_regimes and not f8 and (n, d) == (1 << 20, 768):
         free_b, _ = torch.cuda.mem_get_info()
         if free_b > 40e9:
             regimes = regime(ram, torch, 1 << 24, 768, [4096, 8], k, "bf16", local_rank, [5, 20])
@@ -532,7 +559,7 @@ def main():
             # BASELINE config 5 as it is worded (e4m3 documents, bf16 queries) where bytes bind: the literal HBM-read fraction
             regimes += regime(ram, torch, 1 << 24, 768, [8, 64], k, "fp8_e4m3_docs", local_rank, [20, 20])
             regimes += regime_certified(ram, torch, n, d, nq, local_rank)
-    if world > 1 and not args.no_regimes:
+    if args.full and world > 1 and not args.no_regimes:
         # the configuration the north star quotes scaling on (BASELINE config 3: 2^24 x 768 bf16, row-sharded) and config 5 (e4m3
         # rows) -- measured in this same N-rank run, after the headline, so that the driver's 1/2/4/8 curve carries them
         del index
@@ -550,7 +577,7 @@ def main():
     if rank == 0:
         out = {
             "metric": f"MIPS queries/sec (exact top-{k}, {args.index_dtype} index)", "value": value, "unit": "queries/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": {"bf16": "bf16", "fp8_e4m3": "fp8_e4m3", "fp8_e4m3_docs": "bf16 (e4m3 documents up-converted exactly)"}[args.index_dtype],
             "data": "synthetic",
             "config": {"workload": f"{n}x{d} {args.index_dtype} index (counter-based Gaussian, seed 0xD0C5), Q={nq} bf16 queries "

@@ -2167,7 +2167,7 @@ def test_pitch_1024_pools_over_the_budget_fall_back_to_true_lists():
 
 
 def test_bench_two_rank_line_carries_the_sharded_regimes():
-    """`python bench.py --gpus 2 --backend gloo --rows 65536` (both ranks on this one GPU, host-staged collective): the N > 1
+    """`python bench.py --gpus 2 --backend gloo --rows 65536 --full` (both ranks on this one GPU, host-staged collective): the N > 1
     line keeps the headline contract AND carries `regimes` -- the row-sharded BASELINE config 3 / 5 forms (here at reduced size)
     measured in the same run, with per-GPU shard sizes, scan-kernel times and roofline fractions, the system rate and what
     process group was formed.  This is the line the driver's 1/2/4/8-GPU curve is read from."""
@@ -2179,7 +2179,7 @@ def test_bench_two_rank_line_carries_the_sharded_regimes():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rows", "65536", "--queries", "512",
-                          "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env)
+                          "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0 and line["config"]["rows_per_gpu"] == [32768, 32768]
@@ -2192,6 +2192,30 @@ def test_bench_two_rank_line_carries_the_sharded_regimes():
         assert r["distributed"]["world_size"] == 2 and [g["rows"] for g in r["per_gpu"]] == [131072, 131072]
         for g in r["per_gpu"]:
             assert g["scan_kernel_ms"] > 0 and 0 < g["mfma_frac"] < 1 and 0 < g["hbm_frac"] < 1
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`python bench.py ... --dump-outputs DIR` without --full: the line carries the headline and nothing that takes a run
+    of its own, and DIR holds the last timed step's top-k -- the oracle's answer on the same seeded workload."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    n, d, nq, k = 65536, 768, 64, 5
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", str(n), "--queries", str(nq), "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["full"] is False and line["margin_check"]["unresolved"] == 0
+    assert line["value"] == pytest.approx(nq * 1e3 / line["ms_per_step"])
+    assert line["step_ms"] is None and line["cpu_baseline"] is None and line["regimes"] is None
+    s, i = np.load(tmp_path / "out" / "scores.npy"), np.load(tmp_path / "out" / "indices.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64 and s.shape == i.shape == (nq, k)
+    x = synth.generate(synth.SEED_DOCS, 0, n, d, synth.KIND_GAUSS)
+    q = synth.generate(synth.SEED_QUERIES, 0, nq, d, synth.KIND_GAUSS)
+    es, ei = orc.search_exact(q, x, k)
+    assert np.array_equal(i, ei) and np.array_equal(s, es)
 
 
 # ------------------------------------------------------------------ round 3: a real datasets.Dataset in the loop

@@ -285,6 +285,7 @@ def test_bench_defaults_are_the_baseline_headline_config(monkeypatch):
     a = bench.parse()
     assert (a.gpus, a.rows, a.dim, a.queries, a.k, a.index_dtype) == (1, 1 << 20, 768, 4096, 5, "bf16")
     assert a.steps >= 10 and a.warmup >= 1
+    assert a.full is False and a.dump_outputs is None   # a plain run times the headline only; --full adds the rest
     tree = ast.parse(open(bench.__file__).read())
     for fn in [n for n in tree.body if isinstance(n, ast.FunctionDef)]:
         imports_oracle = any(isinstance(n, ast.ImportFrom) and (n.module or "").startswith("oracle") for n in ast.walk(fn))
@@ -336,8 +337,13 @@ def test_knowledge_base_add_faiss_index_argument_checks():
     kb = ram.KnowledgeBase({"cls": np.zeros((4, 8), np.float32), "aid": list("abcd")})
     with pytest.raises(NotImplementedError, match="Flat"):
         kb.add_faiss_index("cls", string_factory="IVF16,Flat")
-    with pytest.raises(RuntimeError, match="no AMD GPU"):              # a legal build needs the GPU: no CPU fallback
+    if torch.cuda.is_available():                                       # a legal build goes to the device index
         kb.add_faiss_index("cls", metric_type=ram.METRIC_IP)
+        fi = kb.get_index("cls").faiss_index
+        assert isinstance(fi, ram.MipsIndex) and fi.ntotal == 4 and fi.dtype == "f32"
+    else:
+        with pytest.raises(RuntimeError, match="no AMD GPU"):          # a legal build needs the GPU: no CPU fallback
+            kb.add_faiss_index("cls", metric_type=ram.METRIC_IP)
     kb2 = ram.KnowledgeBase({"cls": synth.generate(1, 0, 6, 8, synth.KIND_GAUSS)})
     with pytest.raises(NotImplementedError, match="phi-augmented"):
         kb2.add_faiss_index("cls")                                      # metric None = faiss default L2, rows not augmented

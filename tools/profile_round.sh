@@ -15,5 +15,5 @@ for C in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_
   rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc$i" -- $BENCH --steps 3 --warmup 1 > "$OUT/pmc$i.json" 2> "$OUT/pmc$i.err" || exit 1
   echo "pmc pass $i done" >&2
 done
-python3 bench.py $* --steps 20 --warmup 5 > "$OUT/bench_line.json" 2> "$OUT/bench_line.err" || exit 1
+python3 bench.py --full $* --steps 20 --warmup 5 > "$OUT/bench_line.json" 2> "$OUT/bench_line.err" || exit 1
 python3 tools/profile_summary.py "$OUT"
