@@ -319,10 +319,13 @@ int mips_index_check_error(mips_index_t* index, int synchronize, void* hip_strea
  *      an fp32-exact index then cannot use the scans that rest on the certificate); host-buffer searches still certify.
  * Outputs of the LAST search on the index: flagged = queries flagged by the first pass (-1: only counted on the
  * device and synchronize == 0), rescanned = queries settled exactly (or re-scanned; 0 for a search over its budget whose first
- * results stand), unresolved = queries left with their first result: more than 64 rows tie with the k-th result exactly, or the
- * search flagged more than it resolves.  What an unresolved first result is worth depends on the first scan: true K'-entry
- * lists of bf16 / e4m3 products accumulated in fp32 are exact in practice on tie-free data (the MFMA error observed is
- * ~sqrt(d) 2^-24, two orders of magnitude below the bound); the optimistic scans never leave one behind (mode 1 above).
+ * results stand), unresolved = queries left with their first result: a device-output search flagged more than it resolves
+ * ("resolve_budget"), or -- rows of more than 1024 columns, settled by the re-scan with the widest lists -- the k-th result
+ * ties with more rows than those lists hold.  Floods (more than 64 rows reaching the k-th key: exact ties, or near-duplicates
+ * an optimistic first scan could not separate) are settled exactly like every other flagged query.  What an unresolved first
+ * result is worth depends on the first scan: true K'-entry lists of bf16 / e4m3 products accumulated in fp32 are exact in
+ * practice on tie-free data (the MFMA error observed is ~sqrt(d) 2^-24, two orders of magnitude below the bound); the
+ * optimistic scans over the budget fall back to true lists (mode 1 above).
  * With synchronize != 0 the call also waits for the tail stream of a split-tail search.  Nothing in the reference corresponds (faiss IndexFlat computes its scores in fp32 as well and offers no
  * certificate). */
 int mips_index_margin_stats(mips_index_t* index, int64_t* flagged, int64_t* rescanned, int64_t* unresolved,

@@ -192,6 +192,7 @@ constexpr int kUseRescan = 1;
 // ignore / k_out: the fused hook call's ignore filter (ResolveArgs), d_s / d_i then are [nq][k_out].
 int resolve_flagged(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool certify_now,
                     bool skip_compact = false, const int64_t* ignore = nullptr, int k_out = 0) {
+    if (k > mips::RESOLVE_OVF_K) return fail(MIPS_E_UNSUPPORTED, "resolve_flagged: k = %d exceeds RESOLVE_OVF_K", k);
     int rc = ensure_resolve_buffers(ix, nq); // (never reallocates behind a hand-off: same sizes as tiny_search asked for)
     if (rc) return rc;
     int* ids = (int*)ix->ids.p;
@@ -277,6 +278,17 @@ int resolve_flagged(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i,
     const int fgrid = (int)std::min<int64_t>(nq, certify_now ? (int64_t)ix->nflag_host[0] : (int64_t)a.max_n); // (at least one block: it counts an over-budget search)
     if (l2) mips::resolve_finalize_kernel<true><<<fgrid, 64, 0, st>>>(a);
     else mips::resolve_finalize_kernel<false><<<fgrid, 64, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    // floods (more hits than a hit list holds): one workgroup per RESOLVE_QB flagged slots ranks them over the whole index; the
+    // workgroups of batches without one read RESOLVE_QB counters and leave
+    grid = (fgrid + mips::RESOLVE_QB - 1) / mips::RESOLVE_QB;
+    lds = mips::RESOLVE_QB * a.ld * (int)sizeof(double) + mips::RESOLVE_WAVES * 64 * 9 * 16; // (the plain pass's layout; the lists
+                                                                                            // meet over the tiles)
+    if (f32x) rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemF32, true>) : go(mips::resolve_overflow_kernel<mips::ElemF32, false>);
+    else if (ix->mixed) rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemF8, true, mips::ElemBF16>) : go(mips::resolve_overflow_kernel<mips::ElemF8, false, mips::ElemBF16>);
+    else if (ix->esize == 1) rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemF8, true>) : go(mips::resolve_overflow_kernel<mips::ElemF8, false>);
+    else rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemBF16, true>) : go(mips::resolve_overflow_kernel<mips::ElemBF16, false>);
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     ix->first_nflag_dev = (const int*)cnt;
     ix->last_nflag_dev = unres;

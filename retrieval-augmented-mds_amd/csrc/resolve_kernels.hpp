@@ -18,8 +18,10 @@
 //                         score comes within the error bound of the query's k-th key get the canonical fp64 evaluation (a
 //                         handful per query).  Same hit lists as the kernel above, at the rate the rows stream instead of the
 //                         rate of 8 fp64 FMAs per row element (2.5 - 2.8 TB/s of bf16 rows), and twice the queries per pass.
-//   resolve_finalize_kernel  ranks a query's hits by (key desc, id asc) and overwrites its result row.  More than
-//                         RESOLVE_CAP hits (floods of exact ties) leave the first result in place, counted unresolved.
+//   resolve_finalize_kernel  ranks a query's hits by (key desc, id asc) and overwrites its result row.
+//   resolve_overflow_kernel  the queries with more than RESOLVE_CAP hits (floods: exact ties with the k-th result, or
+//                         near-duplicates an optimistic first scan could not separate): one more pass over the rows per batch
+//                         of RESOLVE_QB slots, a sorted top k per wave, the union ranked in LDS -- the same output rows.
 //
 // Everything is sized on the device (flag list + count from compact_flags_kernel): no synchronisation, graph-capturable;
 // with nothing flagged every workgroup reads the count and leaves.
@@ -80,6 +82,52 @@ __device__ __forceinline__ float resolve_key(double dot, double qq, double phi) 
     return L2 ? -(float)(qq + phi - 2.0 * dot) : (float)dot;
 }
 
+// Canonical dot products of the rows r0 .. r0 + 63 (one per lane; rows past ntotal are clamped, the caller drops them) with
+// the RESOLVE_QB queries in yd (fp64, row pitch ld), each summed sequentially in the column index.  Coalesced: 8 lanes cover
+// the 128-byte segment of one row, 8 rows per load instruction, through the wave's LDS tile ([64 rows][TCH + 1 chunks]);
+// the NEXT segment's loads are in flight while this one is summed (4 waves per CU: nothing else hides the memory round trip).
+template <typename EL>
+__device__ __forceinline__ void exact_dots(const typename EL::type* rows, int ld, int64_t ntotal, int64_t r0, int lane, u32x4* tile,
+                                           const double* yd, double (&acc)[RESOLVE_QB]) {
+    constexpr int PER = EL::PER16; // elements per 16-byte chunk
+    constexpr int TCH = 8;         // chunks per row per tile step: 128 bytes
+    const int nchunk = ld / PER;   // 16-byte chunks per row, a multiple of TCH
+#pragma unroll
+    for (int j = 0; j < RESOLVE_QB; ++j) acc[j] = 0.0;
+    const typename EL::type* src[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        int64_t rr = r0 + 8 * i + (lane >> 3);
+        if (rr >= ntotal) rr = ntotal - 1;
+        src[i] = rows + (size_t)rr * ld + (size_t)(lane & 7) * PER;
+    }
+    u32x4 in[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) in[i] = *reinterpret_cast<const u32x4*>(src[i]);
+    for (int c0 = 0; c0 < nchunk; c0 += TCH) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) tile[(8 * i + (lane >> 3)) * (TCH + 1) + (lane & 7)] = in[i];
+        if (c0 + TCH < nchunk) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) in[i] = *reinterpret_cast<const u32x4*>(src[i] + (size_t)(c0 + TCH) * PER);
+        }
+        __builtin_amdgcn_wave_barrier(); // (one wave: LDS operations complete in order)
+#pragma unroll
+        for (int c = 0; c < TCH; ++c) {
+            const u32x4 v = tile[lane * (TCH + 1) + c];
+            double x[PER];
+#pragma unroll
+            for (int e = 0; e < PER; ++e) x[e] = (double)EL::get(v, e);
+            const double* yy = yd + (size_t)(c0 + c) * PER;
+#pragma unroll
+            for (int j = 0; j < RESOLVE_QB; ++j)
+#pragma unroll
+                for (int e = 0; e < PER; ++e) acc[j] += x[e] * yy[(size_t)j * ld + e]; // sequential in the column index
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
 // RESOLVE_WAVES waves; wave w of workgroup b owns rows (b * RESOLVE_WAVES + w) * 64 .. + 63 of each grid stride
 // (8 waves = two per SIMD: one wave alone cannot cover the LDS round trips between its fp64 chains)
 // ELQ: element type of the staged queries (= EL except for the e4m3-documents / bf16-queries index)
@@ -88,13 +136,11 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void exact_filter_kernel(Resolv
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int n = *a.n_dev;
     if (n == 0 || n > a.max_n) return;
-    constexpr int PER = EL::PER16;               // elements per 16-byte chunk
     constexpr int TCH = 8;                       // chunks per row per tile step: 128 bytes
     double* yd = reinterpret_cast<double*>(smem);                                   // [RESOLVE_QB][ld] queries of the batch, fp64
     unsigned char* tiles = smem + (size_t)RESOLVE_QB * a.ld * sizeof(double);       // [waves][64 rows][TCH + 1 chunks]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     u32x4* tile = reinterpret_cast<u32x4*>(tiles) + wave * 64 * (TCH + 1);
-    const int nchunk = a.ld / PER;               // 16-byte chunks per row, a multiple of TCH
     const typename EL::type* rows = reinterpret_cast<const typename EL::type*>(a.rows);
     const typename ELQ::type* ys = reinterpret_cast<const typename ELQ::type*>(a.y);
     constexpr int PERQ = ELQ::PER16;
@@ -122,42 +168,7 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void exact_filter_kernel(Resolv
         for (int64_t r0 = ((int64_t)blockIdx.x * RESOLVE_WAVES + wave) * 64; r0 < a.ntotal; r0 += (int64_t)gridDim.x * 64 * RESOLVE_WAVES) {
             const int64_t row = r0 + lane;
             double acc[RESOLVE_QB];
-#pragma unroll
-            for (int j = 0; j < RESOLVE_QB; ++j) acc[j] = 0.0;
-            // coalesced: 8 lanes cover the 128-byte segment of one row, 8 rows per load instruction; the NEXT segment's loads
-            // are in flight while this one is summed (4 waves per CU: nothing else hides the memory round trip)
-            const typename EL::type* src[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                int64_t rr = r0 + 8 * i + (lane >> 3);
-                if (rr >= a.ntotal) rr = a.ntotal - 1; // (clamped: the lane's own row test drops it below)
-                src[i] = rows + (size_t)rr * a.ld + (size_t)(lane & 7) * PER;
-            }
-            u32x4 in[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) in[i] = *reinterpret_cast<const u32x4*>(src[i]);
-            for (int c0 = 0; c0 < nchunk; c0 += TCH) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) tile[(8 * i + (lane >> 3)) * (TCH + 1) + (lane & 7)] = in[i];
-                if (c0 + TCH < nchunk) {
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) in[i] = *reinterpret_cast<const u32x4*>(src[i] + (size_t)(c0 + TCH) * PER);
-                }
-                __builtin_amdgcn_wave_barrier(); // (one wave: LDS operations complete in order)
-#pragma unroll
-                for (int c = 0; c < TCH; ++c) {
-                    const u32x4 v = tile[lane * (TCH + 1) + c];
-                    double x[PER];
-#pragma unroll
-                    for (int e = 0; e < PER; ++e) x[e] = (double)EL::get(v, e);
-                    const double* yy = yd + (size_t)(c0 + c) * PER;
-#pragma unroll
-                    for (int j = 0; j < RESOLVE_QB; ++j)
-#pragma unroll
-                        for (int e = 0; e < PER; ++e) acc[j] += x[e] * yy[(size_t)j * a.ld + e]; // sequential in the column index
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
+            exact_dots<EL>(rows, a.ld, a.ntotal, r0, lane, tile, yd, acc);
             if (row < a.ntotal) {
 #pragma unroll
                 for (int j = 0; j < RESOLVE_QB; ++j) {
@@ -360,7 +371,8 @@ __global__ __launch_bounds__(64) void resolve_finalize_kernel(ResolveArgs a) {
     }
     const int c = a.hit_n[j];
     const int q = a.ids[j];
-    if (c > RESOLVE_CAP || c < a.k) { // a flood of ties (or nothing to rank: cannot happen, the current top k always hit)
+    if (c > RESOLVE_CAP) return; // a flood: more hits than the list holds -- resolve_overflow_kernel ranks this query
+    if (c < a.k) {               // nothing to rank (cannot happen: the current top k always hit)
         if (lane == 0) atomicAdd(a.unresolved, 1u);
         return;
     }
@@ -387,6 +399,171 @@ __global__ __launch_bounds__(64) void resolve_finalize_kernel(ResolveArgs a) {
         keep = keep && pos < width;
     }
     if (keep) {
+        const size_t o = (size_t)q * width + pos;
+        if (a.out_packed) {
+            a.out_packed[2 * o] = (int64_t)__float_as_uint(outv);
+            a.out_packed[2 * o + 1] = (int64_t)id + a.idx_offset;
+        } else {
+            a.out_s[o] = outv;
+            a.out_i[o] = (int64_t)id + a.idx_offset;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Floods: flagged queries with more than RESOLVE_CAP hits (rows reaching the current k-th key -- exact ties with the k-th
+// result, or near-duplicates an optimistic first scan could not tell apart).  Workgroup b takes the flagged slots
+// b * RESOLVE_QB .. + RESOLVE_QB - 1 and leaves unless one of them overflowed (nothing else is read: free when nothing does).
+// Otherwise it streams the stored rows once for the batch (exact_dots, the canonical score of every row), and each wave keeps,
+// per query, a sorted top k of the rows reaching the k-th key: (key desc, id asc) in lanes 0 .. k - 1, entries inserted one at
+// a time (ballot of the lanes that beat the wave's current k-th).  The waves' lists meet in LDS, one wave per query ranks
+// their union and writes the row as resolve_finalize_kernel does (ignore filter, k_out, L2 keys, idx_offset, packed).
+// Memory: the lists live in registers and LDS, whatever the flood's size; no scratch in global memory.
+constexpr int RESOLVE_OVF_K = 32; // k of the lists (k + 1 with the ignore filter, <= MIPS_MAX_K + 1)
+
+template <typename EL, bool L2, typename ELQ = EL>
+__global__ __launch_bounds__(64 * RESOLVE_WAVES) void resolve_overflow_kernel(ResolveArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int n = *a.n_dev;
+    if (n == 0 || n > a.max_n) return;
+    const int j0 = blockIdx.x * RESOLVE_QB;
+    if (j0 >= n) return;
+    unsigned ovf = 0u; // the batch's overflowing slots
+#pragma unroll
+    for (int j = 0; j < RESOLVE_QB; ++j)
+        if (j0 + j < n && a.hit_n[j0 + j] > RESOLVE_CAP) ovf |= 1u << j;
+    if (ovf == 0u) return;
+    constexpr int TCH = 8;
+    double* yd = reinterpret_cast<double*>(smem);                                   // [RESOLVE_QB][ld] queries of the batch, fp64
+    unsigned char* tiles = smem + (size_t)RESOLVE_QB * a.ld * sizeof(double);       // [waves][64 rows][TCH + 1 chunks]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    u32x4* tile = reinterpret_cast<u32x4*>(tiles) + wave * 64 * (TCH + 1);
+    const typename EL::type* rows = reinterpret_cast<const typename EL::type*>(a.rows);
+    const typename ELQ::type* ys = reinterpret_cast<const typename ELQ::type*>(a.y);
+    constexpr int PERQ = ELQ::PER16;
+    const int nchunkq = a.ld / PERQ;
+    const int K = a.k;
+
+    // the overflowing queries -> fp64 in LDS (the others: zeros, and a k-th key nothing reaches)
+    for (int t = tid; t < RESOLVE_QB * nchunkq; t += 64 * RESOLVE_WAVES) {
+        const int j = t / nchunkq, c = t % nchunkq;
+        const bool on = (ovf >> j) & 1u;
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (on) v = *reinterpret_cast<const u32x4*>(ys + (size_t)a.ids[j0 + j] * a.ld + (size_t)c * PERQ);
+#pragma unroll
+        for (int e = 0; e < PERQ; ++e) yd[(size_t)j * a.ld + c * PERQ + e] = on ? (double)ELQ::get(v, e) : 0.0;
+    }
+    __syncthreads();
+    float kk[RESOLVE_QB];
+    double qn[RESOLVE_QB];
+#pragma unroll
+    for (int j = 0; j < RESOLVE_QB; ++j) {
+        const int qid = (ovf >> j) & 1u ? a.ids[j0 + j] : -1;
+        kk[j] = qid >= 0 ? a.keyk[qid] : INFINITY;
+        qn[j] = qid >= 0 && L2 ? a.qq[qid] : 0.0;
+    }
+    // the wave's lists: lane t < cnt[j] holds the t-th best of query j
+    float lk[RESOLVE_QB];
+    int li[RESOLVE_QB];
+    double ldot[RESOLVE_QB];
+    int cnt[RESOLVE_QB];
+#pragma unroll
+    for (int j = 0; j < RESOLVE_QB; ++j) {
+        lk[j] = -INFINITY;
+        li[j] = IDX_NONE;
+        ldot[j] = 0.0;
+        cnt[j] = 0;
+    }
+    for (int64_t r0 = (int64_t)wave * 64; r0 < a.ntotal; r0 += 64 * RESOLVE_WAVES) {
+        const int64_t row = r0 + lane;
+        double acc[RESOLVE_QB];
+        exact_dots<EL>(rows, a.ld, a.ntotal, r0, lane, tile, yd, acc);
+#pragma unroll
+        for (int j = 0; j < RESOLVE_QB; ++j) {
+            const float key = resolve_key<L2>(acc[j], qn[j], a.phi);
+            const float wk = __shfl(lk[j], K - 1);
+            const int wi = __shfl(li[j], K - 1);
+            unsigned long long m = __ballot(row < a.ntotal && key >= kk[j] && (cnt[j] < K || ranks_before(key, (int)row, wk, wi)));
+            while (m != 0ull) { // one candidate at a time, in row order, the whole wave on it
+                const int l = __ffsll((long long)m) - 1;
+                m &= m - 1ull;
+                const float nk = __shfl(key, l);
+                const int ni = (int)(r0 + l);
+                const double nd = __shfl(acc[j], l);
+                const int pos = __popcll(__ballot(lane < cnt[j] && ranks_before(lk[j], li[j], nk, ni)));
+                if (pos < K) {
+                    const int src = lane > 0 ? lane - 1 : 0;
+                    const float uk = __shfl(lk[j], src);
+                    const int ui = __shfl(li[j], src);
+                    const double ud = __shfl(ldot[j], src);
+                    if (lane > pos) {
+                        lk[j] = uk;
+                        li[j] = ui;
+                        ldot[j] = ud;
+                    } else if (lane == pos) {
+                        lk[j] = nk;
+                        li[j] = ni;
+                        ldot[j] = nd;
+                    }
+                    cnt[j] = cnt[j] < K ? cnt[j] + 1 : K;
+                }
+            }
+        }
+    }
+    // the waves' lists -> LDS (over the tiles: every wave is past its last one), [j][wave][K] + counts
+    __syncthreads();
+    double* md = reinterpret_cast<double*>(tiles);                      // [RESOLVE_QB][RESOLVE_WAVES][K]
+    float* mk = reinterpret_cast<float*>(md + RESOLVE_QB * RESOLVE_WAVES * K);
+    int* mi = reinterpret_cast<int*>(mk + RESOLVE_QB * RESOLVE_WAVES * K);
+    int* mc = mi + RESOLVE_QB * RESOLVE_WAVES * K;                      // [RESOLVE_QB][RESOLVE_WAVES]
+#pragma unroll
+    for (int j = 0; j < RESOLVE_QB; ++j) {
+        const int o = (j * RESOLVE_WAVES + wave) * K;
+        if (lane < cnt[j]) {
+            md[o + lane] = ldot[j];
+            mk[o + lane] = lk[j];
+            mi[o + lane] = li[j];
+        }
+        if (lane == 0) mc[j * RESOLVE_WAVES + wave] = cnt[j];
+    }
+    __syncthreads();
+    // wave j ranks query j's union (<= RESOLVE_WAVES * K entries, 4 per lane)
+    const int j = wave;
+    if (!((ovf >> j) & 1u)) return;
+    const int q = a.ids[j0 + j];
+    constexpr int PL = RESOLVE_WAVES * RESOLVE_OVF_K / 64;
+    int rank[PL], ent[PL];
+    int rb = 0x7fffffff; // rank of the banned id among the kept entries
+    const int64_t banned = a.ignore != nullptr ? a.ignore[q] : (int64_t)-1;
+#pragma unroll
+    for (int u = 0; u < PL; ++u) {
+        const int e = lane + 64 * u, w = e / K;
+        const bool valid = e < RESOLVE_WAVES * K && (e - w * K) < mc[j * RESOLVE_WAVES + w];
+        ent[u] = valid ? (j * RESOLVE_WAVES) * K + e : -1;
+        int r = 0x7fffffff;
+        if (valid) {
+            const float ck = mk[ent[u]];
+            const int ci = mi[ent[u]];
+            r = 0;
+            for (int w2 = 0; w2 < RESOLVE_WAVES; ++w2) {
+                const int c2 = mc[j * RESOLVE_WAVES + w2], o2 = (j * RESOLVE_WAVES + w2) * K;
+                for (int t = 0; t < c2; ++t) r += ranks_before(mk[o2 + t], mi[o2 + t], ck, ci) ? 1 : 0;
+            }
+        }
+        rank[u] = r;
+        const unsigned long long bb = __ballot(a.ignore != nullptr && valid && r < K && (int64_t)mi[ent[u]] + a.idx_offset == banned);
+        if (bb != 0ull) rb = __shfl(r, __ffsll((long long)bb) - 1);
+    }
+    const double qq = L2 ? a.qq[q] : 0.0;
+    const int width = a.ignore != nullptr ? a.k_out : K;
+#pragma unroll
+    for (int u = 0; u < PL; ++u) {
+        if (ent[u] < 0 || rank[u] >= K || rank[u] == rb) continue;
+        const int pos = rank[u] - (rank[u] > rb ? 1 : 0);
+        if (pos >= width) continue;
+        const double dot = md[ent[u]];
+        const int id = mi[ent[u]];
+        const float outv = L2 ? (float)(qq + a.phi - 2.0 * dot) : (float)dot;
         const size_t o = (size_t)q * width + pos;
         if (a.out_packed) {
             a.out_packed[2 * o] = (int64_t)__float_as_uint(outv);
