@@ -79,6 +79,7 @@ extern "C" {
 #define MIPS_IDX_POISON (-2)
 
 #define MIPS_MAX_K 29 /* largest k one mips_search call accepts */
+#define MIPS_MAX_K_WIDE 1024 /* largest k one mips_search_wide call accepts */
 
 typedef struct mips_index mips_index_t;
 
@@ -179,6 +180,24 @@ int mips_search(mips_index_t* index, const void* q, int q_dtype, int64_t nq, int
  * reference corresponds. */
 int mips_search_split(mips_index_t* index, const void* q, int q_dtype, int64_t nq, int k, float* out_scores,
                       int64_t* out_idx, int64_t idx_offset, int flags, void* scan_stream, void* tail_stream);
+
+/* Exact WIDE top-k search: mips_search for k up to MIPS_MAX_K_WIDE -- what faiss IndexFlat.search does for retrieve-then-rerank,
+ * recall@100 / @1000 evaluation and hard-negative mining.  Arguments and results as mips_search (same canonical score, same order
+ * and tie rule, same padding; for k <= MIPS_MAX_K the output equals mips_search bit for bit).  Served: bf16 and fp32-exact
+ * indexes of at most 1024 columns, both metrics, F32 / BF16 queries in host or device memory, MIPS_FORCE_IP, MIPS_Q_DEVICE,
+ * MIPS_OUT_DEVICE, idx_offset.  MIPS_E_UNSUPPORTED: k > MIPS_MAX_K_WIDE, e4m3 storage, MIPS_OUT_PACKED, rows of more than 1024
+ * columns.
+ * How: the index is walked in row chunks; a threshold scan (bf16 MFMA; the bf16 image of an fp32-exact index) appends every row
+ * scoring above the query's threshold to that query's candidate segments, a select keeps the best k' = k + slack per query and
+ * raises the threshold, the k' survivors are re-scored canonically and ranked (DESIGN.md "Wide top-k").  EVERY wide search is
+ * certified, whatever "margin_check" says: a query for which a row outside the pool cannot be proven to rank behind the k-th
+ * result is settled exactly, by brute force on the canonical scores, in the same call; mips_index_margin_stats then reports
+ * flagged = rescanned = the number of such queries and unresolved = 0, always.  Device-output calls enqueue everything on the
+ * stream and never synchronise (flag list and count live on the device); host-output calls synchronise once, at the end.
+ * Scratch: a fixed budget (256 MiB of candidate segments) plus O(nq k); more than 4096 queries are processed in slices.
+ * mips_index_last_kernel names the wide scan kernel afterwards. */
+int mips_search_wide(mips_index_t* index, const void* q, int q_dtype, int64_t nq, int k, float* out_scores,
+                     int64_t* out_idx, int64_t idx_offset, int flags, void* hip_stream);
 
 /* The device-resident scoring hook in one call: what retriever_generator.py:143-153 -> mips.py:421-422 does per
  * training / generation step -- `_prepare_query` (row normalisation for the normalised inner-product index,

@@ -27,6 +27,7 @@ Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP = 1, 2, 4, 8
 SYNTH_LATTICE, SYNTH_GAUSS, SYNTH_LATTICE_FP8 = 0, 1, 2
 SEED_DOCS, SEED_QUERIES = 0xD0C5, 0x0E21  # fixed seeds of the synthetic workloads
 MAX_K = 29
+MAX_K_WIDE = 1024  # MIPS_MAX_K_WIDE: largest k of mips_search_wide
 IDX_POISON = -2  # MIPS_IDX_POISON: what a search whose scan kernel timed out returns in every slot
 
 _lock = threading.Lock()
@@ -124,6 +125,7 @@ def _bind(lib):
         "mips_index_add_synthetic": (i32, [vp, i64, i64, u64, i32, vp]),
         "mips_synth_fill": (i32, [vp, i64, i64, i64, u64, i32, i32, i32, vp]),
         "mips_search": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp]),
+        "mips_search_wide": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp]),
         "mips_search_split": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, vp]),
         "mips_search_fused": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp, i64, vp]),
         "mips_merge_topk": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, i32, vp]),
@@ -155,7 +157,7 @@ EXPORTS = (
     "mips_index_add_synthetic", "mips_synth_fill", "mips_search", "mips_merge_topk",
     "mips_merge_topk_packed", "mips_filter_ignore", "mips_cosine_rescore", "mips_cosine_rescore_bias", "mips_l2_normalize", "mips_rows_max_sumsq", "mips_index_set_param", "mips_scan_timing",
     "mips_index_check_error", "mips_index_last_kernel", "mips_cosine_rescore_backward", "mips_index_margin_stats", "mips_search_fused", "mips_search_split",
-    "mips_rows_max_sumsq_device",
+    "mips_rows_max_sumsq_device", "mips_search_wide",
 )
 
 

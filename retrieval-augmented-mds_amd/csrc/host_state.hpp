@@ -136,6 +136,9 @@ struct mips_index {
     // synchronise anyway) unless the check is off.
     int opt_margin = 1;
     Buffer mbnd, mflag, qbuf2, qf32b, tmp_s, tmp_i, ids, qhi, qerr2, keyk, qqv, hit_d, hit_i, hit_n, qnorm;
+    // wide top-k (mips_search_wide, host_wide.hpp): candidate segments (fixed budget), pools [queries][k'], segment counters,
+    // per-query thresholds / seeds / flags
+    Buffer w_seg, w_pool, w_cnt, w_misc;
     int opt_resolve = 1; // flagged queries: 1 = exact brute-force resolution (resolve_kernels.hpp; 2 = its plain form, no MFMA pre-filter), 0 = re-scan with the widest lists
     int resolve_budget = 0; // "resolve_budget" > 0: flagged queries a search resolves at most (0 = RESOLVE_MAX); a search that flags
                             // more keeps its first results (counted unresolved) -- or, if its first scan was an optimistic one,

@@ -28,10 +28,12 @@
 #include "scan_kernel_e8.hpp"
 #include "tiny_search.hpp"
 #include "resolve_kernels.hpp"
+#include "scan_kernel_wide.hpp"
 
 #include "host_state.hpp"
 #include "host_launch.hpp"
 #include "host_search.hpp"
+#include "host_wide.hpp"
 
 extern "C" {
 
@@ -139,6 +141,10 @@ int mips_index_destroy(mips_index_t* ix) {
     ix->hit_i.release();
     ix->hit_n.release();
     ix->qnorm.release();
+    ix->w_seg.release();
+    ix->w_pool.release();
+    ix->w_cnt.release();
+    ix->w_misc.release();
     for (int e = 0; e < mips_index::kEvRing; ++e) {
         if (ix->ev0[e]) (void)hipEventDestroy(ix->ev0[e]);
         if (ix->ev1[e]) (void)hipEventDestroy(ix->ev1[e]);
@@ -494,6 +500,68 @@ static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq,
         // host buffers: the stream is drained, so a timed-out scan of THIS call is known now
         const int bad = take_scan_error(ix, "mips_search");
         if (bad) return bad;
+    }
+    return MIPS_OK;
+}
+
+int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                     int64_t idx_offset, int flags, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "mips_search_wide: index is NULL");
+    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_search_wide: negative nq or k");
+    if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: k = %d exceeds MIPS_MAX_K_WIDE = %d", k, MIPS_MAX_K_WIDE);
+    if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: e4m3 storage is not served (bf16 and fp32-exact indexes only)");
+    if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: no packed output");
+    if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
+        return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: stored rows of more than 1024 columns are not served");
+    if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "mips_search_wide: q_dtype must be F32 or BF16");
+    if (nq == 0 || k == 0) return MIPS_OK;
+    if (!q || !out_idx || !out_scores) return fail(MIPS_E_INVALID, "mips_search_wide: NULL buffer");
+    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: more than 2^24 queries in one call");
+    DeviceGuard g(ix->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    {
+        const int prev = take_scan_error(ix, "mips_search_wide");
+        if (prev) return prev;
+    }
+    ORDER_ON(ix, st);
+    if (ix->tail_pending[ix->cur_set]) { // a split-tail search still reading the staged queries of this scratch set
+        HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[ix->cur_set], 0));
+        ix->tail_pending[ix->cur_set] = false;
+    }
+    const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
+    ix->call_metric = (flags & MIPS_FORCE_IP) ? MIPS_METRIC_IP : ix->metric;
+    float* d_s = out_scores;
+    int64_t* d_i = out_idx;
+    if (!out_dev) {
+        int rc = ix->out_s.ensure((size_t)nq * k * sizeof(float));
+        if (rc) return rc;
+        rc = ix->out_i.ensure((size_t)nq * k * sizeof(int64_t));
+        if (rc) return rc;
+        d_s = (float*)ix->out_s.p;
+        d_i = (int64_t*)ix->out_i.p;
+    }
+    if (ix->ntotal == 0) {
+        const int64_t total = nq * k;
+        mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, nullptr, total, ix->call_metric);
+        HIP_TRY(hipGetLastError());
+        ix->last_flagged = 0;
+        ix->last_rescanned = 0;
+        ix->last_unresolved = 0;
+        ix->first_nflag_dev = nullptr;
+    } else {
+        const int rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, idx_offset, (flags & MIPS_Q_DEVICE) != 0, st);
+        if (rc) return rc;
+    }
+    if (!out_dev) {
+        if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host, 64, hipHostMallocDefault));
+        HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (ix->ntotal > 0) HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->first_nflag_dev, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (ix->ntotal > 0) {
+            ix->last_flagged = (int64_t)ix->nflag_host[0];
+            ix->last_rescanned = ix->last_flagged;
+        }
     }
     return MIPS_OK;
 }

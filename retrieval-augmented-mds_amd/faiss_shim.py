@@ -120,7 +120,9 @@ class IndexFlat:
                 raise ValueError("L2 search: the queries' last (augmentation) column is not zero; this index answers queries "
                                  "prepared by augment_xq (sotasum/mips.py:68-70)")
             q = np.ascontiguousarray(q[:, :-1])
-        return ix.search(q, int(k))
+        from .index import route_search
+
+        return route_search(ix, q, int(k))   # k > MAX_K: the wide search (k <= MAX_K_WIDE = 1024)
 
 
 class IndexFlatIP(IndexFlat):

@@ -29,6 +29,14 @@ def _stream_handle(device: int) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def route_search(index, q, k: int, **kwargs):
+    """index.search(q, k), or index.search_wide(q, k) when k exceeds MAX_K and the index has a wide search (MipsIndex does;
+    ShardedMipsIndex and foreign duck-typed indexes keep their own search and its limits)."""
+    if int(k) > _lib.MAX_K and hasattr(index, "search_wide"):
+        return index.search_wide(q, int(k), **kwargs)
+    return index.search(q, k, **kwargs)
+
+
 class MipsIndex:
     def __init__(self, d: int, metric: int = _lib.METRIC_IP, dtype: str = "bf16", device: int | None = None):
         if dtype not in ("bf16", "fp8_e4m3", "fp8_e4m3_docs", "f32"):
@@ -201,6 +209,42 @@ class MipsIndex:
             else:
                 _lib.check(self._lib.mips_search(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags, stream),
                            "mips_search")
+        del keep
+        return D, I
+
+    def search_wide(self, x, k: int, idx_offset: int = 0, force_ip: bool = False):
+        """search() for k up to MAX_K_WIDE = 1024 (mips_search_wide: threshold scan, streaming select, exact re-score; every
+        query certified or settled exactly in the same call).  bf16 and f32 indexes of at most 1024 columns.  NumPy in ->
+        NumPy out; torch CUDA tensor in -> torch CUDA tensors out, stream-ordered, no synchronisation."""
+        import torch
+
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must be >= 0")
+        if k > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"k = {k} > {_lib.MAX_K_WIDE} is not supported by this build")
+        if self._f8:
+            raise NotImplementedError("search_wide serves 'bf16' and 'f32' indexes; e4m3 storage is limited to search()")
+        if self._d > 1024:
+            raise NotImplementedError("search_wide serves rows of at most 1024 columns")
+        ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        stream = _stream_handle(self.device)
+        if is_dev:
+            dev = f"cuda:{self.device}"
+            D = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            I = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            flags = _lib.Q_DEVICE | _lib.OUT_DEVICE
+            ds, di = D.data_ptr(), I.data_ptr()
+        else:
+            D = np.empty((nq, k), dtype=np.float32)
+            I = np.empty((nq, k), dtype=np.int64)
+            flags = 0
+            ds, di = D.ctypes.data, I.ctypes.data
+        if force_ip:
+            flags |= _lib.FORCE_IP
+        with self._mutex:
+            _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags, stream),
+                       "mips_search_wide")
         del keep
         return D, I
 

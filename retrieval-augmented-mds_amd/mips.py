@@ -34,7 +34,7 @@ from random import random
 import numpy as np
 
 from . import _lib
-from .index import MipsIndex, l2_normalize_, rows_max_sumsq, rows_max_sumsq_into
+from .index import MipsIndex, l2_normalize_, route_search, rows_max_sumsq, rows_max_sumsq_into
 
 METRIC_INNER_PRODUCT = _lib.METRIC_IP
 METRIC_L2 = _lib.METRIC_L2
@@ -139,7 +139,7 @@ def inner_product(x: np.ndarray, y: np.ndarray, k: int = 1, normalize: bool = Tr
         l2_normalize_(yd)
     ix = MipsIndex(y.shape[1], metric=METRIC_INNER_PRODUCT, dtype=dtype, device=device)
     ix.add(yd)
-    s, i = ix.search(xd, k)
+    s, i = route_search(ix, xd, k)
     return s.cpu().numpy(), i.cpu().numpy()
 
 
@@ -277,7 +277,7 @@ class KnowledgeBase:
         L2 indexes take the reference's augmented queries ([B, d + 1], zero last column) as they come."""
         index = self.get_index(index_name).faiss_index
         q = _strip_augmentation_column(index, np.asarray(queries, dtype=np.float32))
-        s, i = index.search(np.ascontiguousarray(q), k)
+        s, i = route_search(index, np.ascontiguousarray(q), k)
         scores, examples = [], []
         for row_s, row_i in zip(s, i):
             keep = row_i >= 0
@@ -574,7 +574,7 @@ class Mips:
         equal to ignore_indexes[j] is dropped per query and the rest cut to k (lists of lists)."""
         index = self._index()
         q = _strip_augmentation_column(index, np.asarray(queries))  # the zero column of augment_xq
-        scores, indices = index.search(q, k + 1 if ignore_indexes is not None else k)
+        scores, indices = route_search(index, q, k + 1 if ignore_indexes is not None else k)
         if ignore_indexes is not None:
             out_s, out_i = [], []
             for j in range(len(indices)):
@@ -625,7 +625,7 @@ class Mips:
         q = np.array(x, dtype=np.float32, copy=True)
         if self.normalize:
             q = self.l2_normalization(q)
-        return index.search(q, k, force_ip=True)  # the reference's cross-check is always an inner product
+        return route_search(index, q, k, force_ip=True)  # the reference's cross-check is always an inner product
 
     # ------------------------------------------------------------------ forward (mips.py:402-463)
     def forward(self, queries: np.ndarray, aid: list = None, aid_counts=None, target_str: list = None,
