@@ -94,9 +94,14 @@ int launch_e8(mips_index* ix, const mips::ScanArgsE8& fa, int grid, const E8Conf
         kern<<<grid, 512, lds, st>>>(fa);
         return MIPS_OK;
     };
+    // The 16- and 32-query tiles hold the whole search (e8_config ties the tile to nq), so their document blocks always have a single
+    // reader: only the non-temporal instance exists.  Shared blocks (nt = false) are the 64-query tile's alone.
 #define MIPS_E8_ROW(LDB, NCB, STG, PIPE, KW)                                               \
-    if (c.ncb == NCB && c.stages == STG && c.pipe == PIPE && c.kw == KW)                   \
-        return nt ? go(mips::scan_kernel_e8<6, LDB, NCB, STG, true, PUB, PIPE, KW>) : go(mips::scan_kernel_e8<6, LDB, NCB, STG, false, PUB, PIPE, KW>)
+    if (c.ncb == NCB && c.stages == STG && c.pipe == PIPE && c.kw == KW) {                 \
+        if (nt) return go(mips::scan_kernel_e8<6, LDB, NCB, STG, true, PUB, PIPE, KW>);    \
+        if constexpr (NCB == 4) return go(mips::scan_kernel_e8<6, LDB, NCB, STG, false, PUB, PIPE, KW>); \
+        return fail(MIPS_E_UNSUPPORTED, "e4m3-documents index: a %d-query tile never shares its document blocks", 16 * NCB); \
+    }
 #ifdef MIPS_EXPERIMENTAL
 #define MIPS_E8_OLD(LDB)                                                        \
         MIPS_E8_ROW(LDB, 2, 3, (LDB <= 768), 8);                                \
