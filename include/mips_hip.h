@@ -278,8 +278,8 @@ int mips_rows_max_sumsq_device(const float* x_device, int64_t n, int64_t d, doub
 /* Tuning knobs of the scan launch (0 = automatic): "nsplit" = number of index splits (rounded up
  * to a multiple of 8), "qgroups" = query-tile groups per XCD octet (1, 2, 4 or 8), "variant" = scan kernel (1 = 128x128
  * register-staged tiles, 3 = query-stationary on the 32x32x16 MFMA shape, 4 = query-stationary on the
- * 16x16x32 shape (d padding to 384 .. 768, k <= 5), 7 = wave pairs splitting K at row pitch 1024 (k <= 5); 5 and 6 name
- * measured alternatives that exist in the A/B build of tools/ab.py only and are ignored here).  Results never depend on
+ * 16x16x32 shape (d padding to 384 .. 768, k <= 5), 7 = wave pairs splitting K at row pitch 1024 (k <= 5); 5 and 6 named
+ * measured alternatives of the retired A/B build and are treated as 0).  Results never depend on
  * these four; only speed does.
  * "margin_check" (0 .. 4) selects what happens to queries whose candidate pool is not provably wide enough: see
  * mips_index_margin_stats.  "resolve_budget" (default 0 = 1024): flagged queries one search settles at most.
@@ -295,10 +295,9 @@ int mips_rows_max_sumsq_device(const float* x_device, int64_t n, int64_t d, doub
  *                 value makes the kernel give up spuriously and -1 makes every scan launch raise its error word
  *                 unconditionally -- that is their purpose: tests use them to drive the MIPS_E_SCAN_TIMEOUT /
  *                 MIPS_IDX_POISON path.  Never set it in production.
- *   "sub"         A/B selector of experimental kernel instances (profiles/ experiment logs), two of which skip the
- *                 top-k epilogue and return wrong results by design.  The shipped library does not contain them:
- *                 any value but 0 returns MIPS_E_UNSUPPORTED unless the library was built with -DMIPS_EXPERIMENTAL
- *                 (tools/ab.py does that into tools/_build/). */
+ *   "sub"         was the A/B selector of experimental kernel instances (the experiment logs under profiles/), several
+ *                 of which returned wrong results by design.  The A/B build was retired: 0 is accepted, any other value
+ *                 returns MIPS_E_UNSUPPORTED.  Commit 29d81a63fdff is the last one those instances can be rebuilt from. */
 int mips_index_set_param(mips_index_t* index, const char* name, int64_t value);
 
 /* Scan-error check.  The fused scan kernels synchronise their waves per document block through a bounded poll; a

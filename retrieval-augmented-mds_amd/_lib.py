@@ -52,29 +52,10 @@ def _stale() -> bool:
 # -amdgpu-mfma-vgpr-form: MFMA results in architectural VGPRs even in kernels that pin values in AGPRs.  The
 # query-stationary kernels fill the AGPR half of the register file with stationary B fragments (inline-asm "a"
 # constraints); without the option LLVM then selects the AGPR-destination MFMA forms for the whole kernel, the
-# accumulators compete with the fragments for AGPRs and scan_kernel_v5 spills fragments (reloaded behind a vmcnt(0)
-# that drains the LDS-DMA ring); with it: 254 VGPRs + 256 AGPRs, no scratch.  No other kernel changes its spill count.
+# accumulators compete with the fragments for AGPRs (the retired 64-queries-per-wave kernel spilled fragments, reloaded
+# behind a vmcnt(0) that drains the LDS-DMA ring; with it: 254 VGPRs + 256 AGPRs, no scratch).  The shipped kernels were
+# measured and tuned with the option; none changes its spill count.
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-shared", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]
-
-EXP_LIB_PATH = os.path.join(_ROOT, "tools", "_build", "libmips_hip_exp.so")
-
-
-def build_experimental(verbose: bool = False) -> str:
-    """The A/B build for tools/ab.py: the same source with -DMIPS_EXPERIMENTAL (the `sub` instances of the
-    experiment logs under profiles/, two of which return wrong results by design).  Never loaded by the product
-    unless MIPS_HIP_EXPERIMENTAL=1 is set in the environment."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    os.makedirs(os.path.dirname(EXP_LIB_PATH), exist_ok=True)
-    if os.path.exists(EXP_LIB_PATH) and all(os.path.getmtime(s) <= os.path.getmtime(EXP_LIB_PATH) for s in _sources()):
-        return EXP_LIB_PATH
-    cmd = [hipcc, *HIPCC_FLAGS, "-DMIPS_EXPERIMENTAL", "-o", EXP_LIB_PATH, os.path.join(CSRC, "mips_hip.hip")]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    proc = subprocess.run(cmd, capture_output=True, text=True)
-    if proc.returncode != 0:
-        raise RuntimeError(f"hipcc failed ({proc.returncode}):\n{proc.stderr[-4000:]}")
-    return EXP_LIB_PATH
-
 
 def build(force: bool = False, verbose: bool = False) -> str:
     """hipcc --offload-arch=gfx950 csrc/mips_hip.hip -> lib/libmips_hip.so (in-tree)."""
@@ -172,8 +153,7 @@ def load():
             return _lib
         import torch  # noqa: F401  (must precede dlopen, see docstring)
 
-        path = build_experimental() if os.environ.get("MIPS_HIP_EXPERIMENTAL") == "1" else build()
-        lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
+        lib = ctypes.CDLL(build(), mode=ctypes.RTLD_GLOBAL)
         _bind(lib)
         ver = lib.mips_abi_version()
         if ver != ABI_VERSION:

@@ -141,13 +141,6 @@ int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int 
         return fail(MIPS_E_INVALID, "tiny_search: the fp32-exact index needs the margin check");
     }
     const int lds = mips::tiny_lds_bytes(tld, ix->plane);
-#ifdef MIPS_EXPERIMENTAL
-    static unsigned long long* dbg_dev = nullptr;
-    const bool dbg = getenv("MIPS_TINY_DBG") != nullptr;
-    if (dbg && !dbg_dev) HIP_TRY(hipMalloc((void**)&dbg_dev, 256 * 16 * 8));
-    a.dbg = dbg ? dbg_dev : nullptr;
-    if (dbg) HIP_TRY(hipMemsetAsync(dbg_dev, 0, 256 * 16 * 8, st));
-#endif
     auto go = [&](auto kern) -> int {
         if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         kern<<<nwg, mips::TINY_THREADS, lds, st>>>(a);
@@ -158,26 +151,6 @@ int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int 
     else rc = l2m ? go(mips::tiny_search_kernel<true, false>) : go(mips::tiny_search_kernel<false, false>);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
-#ifdef MIPS_EXPERIMENTAL
-    if (dbg) { // phase stamps (10 ns units) relative to the first workgroup's start: the slowest workgroup per phase and the last one
-        std::vector<unsigned long long> h(256 * 16);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(h.data(), dbg_dev, 256 * 16 * 8, hipMemcpyDeviceToHost));
-        unsigned long long t0 = ~0ull;
-        int last = 0;
-        for (int b = 0; b < nwg; ++b) {
-            t0 = std::min(t0, h[b * 16]);
-            if (h[b * 16 + 11]) last = b;
-        }
-        unsigned long long mx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int b = 0; b < nwg; ++b)
-            for (int i = 0; i < 8; ++i) mx[i] = std::max(mx[i], h[b * 16 + i] - t0);
-        fprintf(stderr, "tiny x10ns max/%d wgs: start %llu docs-issued %llu zero-rows %llu rows-staged %llu barrier %llu scanned %llu selected %llu ticket %llu | last wg %d: ticket %llu select2 %llu dots %llu ranked %llu end %llu | shader clock %.0f MHz\n",
-                nwg, mx[0], mx[1], mx[2], mx[3], mx[4], mx[5], mx[6], mx[7], last, h[last * 16 + 7] - t0, h[last * 16 + 8] - t0,
-                h[last * 16 + 9] - t0, h[last * 16 + 10] - t0, h[last * 16 + 11] - t0,
-                (double)(h[last * 16 + 13] - h[last * 16 + 12]) / ((double)(h[last * 16 + 11] - h[last * 16]) * 0.01));
-    }
-#endif
     set_kernel_name(ix, "mips::tiny_search_kernel<%s, %s>", l2m ? "true" : "false", f32x ? "true" : "false");
     return MIPS_OK;
 }

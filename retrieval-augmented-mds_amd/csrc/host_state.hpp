@@ -124,7 +124,6 @@ struct mips_index {
     int opt_nsplit = 0;
     int opt_qgroups = 0;
     size_t err_off = 0; // word offset of the scan kernel's error flag inside gthr (0 = none this call)
-    int opt_sub = 0;
     int opt_spin_limit = 0; // test-only: polls of the split barrier before a wave gives up (0 = 1 << 22, < 0 = flag forced)
     // sticky scan-error flag: one pinned, mapped host word.  The exact re-score sets it (system-scope store) when
     // the scan kernel of its call gave up on the split barrier; the host reads it without a device round trip.

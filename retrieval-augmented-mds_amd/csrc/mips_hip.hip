@@ -20,10 +20,6 @@
 #include "scan_kernel_f8.hpp"
 #include "scan_kernel_f8x.hpp"
 #include "scan_kernel_v4.hpp"
-#ifdef MIPS_EXPERIMENTAL // measured alternatives that never became a default (profiles/r2_v5_64q, r2_pitch1024): A/B library only
-#include "scan_kernel_v5.hpp"
-#include "scan_kernel_ks.hpp"
-#endif
 #include "scan_kernel_k3.hpp"
 #include "scan_kernel_e8.hpp"
 #include "tiny_search.hpp"
@@ -463,8 +459,8 @@ static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq,
         // to the 8th best approximate one for one Gaussian query in ~3000 at 2^22 rows, and each flagged query costs a pass over the
         // index (3 ms there); the 16th best is out of reach.  Small indexes keep the pool of 8 (their exact pass is cheap).
         bool deep_1024 = !fast && k <= 5 && ix->plane == 0 && ix->esize == 2 && !ix->mixed && ix->ld == 1024 && nq > 256 && ix->ntotal >= (1ll << 21) &&
-                         ix->opt_margin != 0 && !split && (!out_dev || ix->opt_margin >= 2) && ix->opt_f32_fast != 0 && ix->opt_sub == 0 &&
-                         ix->opt_variant == 0; // (forced kernels and the A/B instances keep the pool of 8)
+                         ix->opt_margin != 0 && !split && (!out_dev || ix->opt_margin >= 2) && ix->opt_f32_fast != 0 &&
+                         ix->opt_variant == 0; // (forced kernels keep the pool of 8)
         if (deep_1024 && ix->fast_skip > 0) {
             --ix->fast_skip;
             deep_1024 = false;
@@ -774,9 +770,7 @@ int mips_index_set_param(mips_index_t* ix, const char* name, int64_t value) {
     else if (n == "qgroups") ix->opt_qgroups = (int)value;
     else if (n == "variant") {
         ix->opt_variant = (int)value;
-#ifndef MIPS_EXPERIMENTAL
-        if (value == 5 || value == 6) ix->opt_variant = 0; // (kernels of the A/B build only: the automatic choice answers)
-#endif
+        if (value == 5 || value == 6) ix->opt_variant = 0; // (kernels of the retired A/B build: the automatic choice answers)
     }
     else if (n == "tiny") ix->opt_tiny = value == 2 ? 2 : value != 0 ? 1 : 0; // 2: one launch, fall-back paths forced (tests)
     else if (n == "resolve") ix->opt_resolve = value < 0 ? 0 : value > 2 ? 2 : (int)value; // 2: exact pass without the MFMA pre-filter
@@ -792,13 +786,9 @@ int mips_index_set_param(mips_index_t* ix, const char* name, int64_t value) {
         ix->resolve_budget = (int)std::min<int64_t>(value, mips::RESOLVE_MAX);
     } else if (n == "spin_limit") ix->opt_spin_limit = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 30));
     else if (n == "sub") {
-#ifdef MIPS_EXPERIMENTAL
-        ix->opt_sub = (int)value;
-#else
         if (value != 0)
-            return fail(MIPS_E_UNSUPPORTED, "mips_index_set_param: 'sub' selects experimental kernel instances that the shipped "
-                                            "library does not contain (build with -DMIPS_EXPERIMENTAL, tools/ab.py)");
-#endif
+            return fail(MIPS_E_UNSUPPORTED, "mips_index_set_param: 'sub' selected experimental kernel instances of the A/B build, "
+                                            "which was retired; rebuild them from commit 29d81a6 (the last one that carries them)");
     } else return fail(MIPS_E_INVALID, "mips_index_set_param: unknown parameter '%s'", name);
     return MIPS_OK;
 }

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_f8(ScanArgsF8 pa) {
         li[i] = IDX_NONE;
     }
 
-    // shared per-query thresholds: class maxima, 8 words per query, sparse re-read (scan_kernel_v3.hpp, TMODE 2)
+    // shared per-query thresholds: class maxima, 8 words per query, sparse re-read (scan_kernel_v3.hpp, "shared per-query thresholds")
     constexpr int PUB = (KL + 7) / 8; // a list publishes its PUB-th best: 8 classes x PUB >= K' documents
     static_assert(8 * PUB >= KL, "the class words must prove at least K' documents");
     constexpr unsigned THR_AREA = STAGES * STAGE_BYTES;

@@ -33,7 +33,9 @@ namespace mips {
 constexpr int F8X_DB = 64; // documents per block
 
 // NT_DOCS: non-temporal document DMA for searches of ONE query tile (every block has a single reader)
-template <int KL, int LD, int AD, int TIMING_MODE = 0, bool NT_DOCS = false>
+// (the fourth slot held a diagnostic axis, retired; it stays in the parameter list so that the instance names remain the ones
+// profiles/, latest_traffic.json and the tests know)
+template <int KL, int LD, int AD, int = 0, bool NT_DOCS = false>
 __global__ __launch_bounds__(512, 2) void scan_kernel_f8x(ScanArgsF8 pa) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const ScanArgs& p = pa.c;
@@ -100,7 +102,7 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_f8x(ScanArgsF8 pa) {
         }
     }
 
-    // ---- shared insert bounds (scan_kernel_v3.hpp, TMODE 2): p.gthr = [query tile][wave][32 queries][8 words]
+    // ---- shared insert bounds (scan_kernel_v3.hpp, "shared per-query thresholds"): p.gthr = [query tile][wave][32 queries][8 words]
     constexpr unsigned THR_AREA = STAGES * STAGE_BYTES;
     constexpr unsigned THR_WAVE = 1024u;
     constexpr unsigned DUMP_AREA = THR_AREA + WAVES * THR_WAVE;
@@ -198,13 +200,6 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_f8x(ScanArgsF8 pa) {
             __builtin_amdgcn_sched_barrier(0);
         }
         arrive(); // chain done, share of the next block landed; the epilogue below runs un-synchronised
-        if (TIMING_MODE == 1) { // diagnostic build (results are wrong): no epilogue at all
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-            for (int tl = 0; tl < TILES; ++tl) asm volatile("" ::"v"(acc[tl][0]), "v"(acc[tl][1]));
-#endif
-            return;
-        }
         const int base = blk * F8X_DB + (int)((thr_addr >> 6) & 12u); // + 4 g, from the lane bits of thr_addr
         if ((int64_t)(blk + 1) * F8X_DB > p.ntotal) { // last block of the index only
 #pragma unroll

@@ -1,10 +1,10 @@
-// scan_kernel_k3: row pitch 1024 with 192 STATIONARY QUERIES per CU (scan_kernel_ks's wave pairs, three 16-query blocks each).
+// scan_kernel_k3: row pitch 1024 with 192 STATIONARY QUERIES per CU (wave pairs splitting K, three 16-query blocks each).
 //
 // Why (profiles/r2_pitch1024, profiles/r3_pitch1024): at pitch 1024 a 32-document block is 64 KiB.  With 128 stationary queries
 // per CU (all the 1024-wide fragments the register file holds at 32 queries per wave) the MFMAs of a block take 2048 cycles per
 // SIMD at full rate -- 32 B/clk/CU of L2 -> LDS fill, above what a CU's LDS-DMA path sustains (~28 B/clk): scan_kernel_v3's 4-wave
-// configuration and scan_kernel_ks both sit at 0.45-0.47 of the MFMA peak whatever the wave schedule.  The cure is more flops
-// per streamed byte: a wave PAIR splits K (512 columns each, as in scan_kernel_ks) but shares 48 queries instead of 32 -- three
+// configuration and the first K-split kernel (wave pairs of 32 queries, retired) both sat at 0.45-0.47 of the MFMA peak whatever the wave schedule.  The cure is more flops
+// per streamed byte: a wave PAIR splits K (512 columns each) but shares 48 queries instead of 32 -- three
 // 16-query column blocks x 16 k32-steps = 48 fragments = 192 registers per wave, what scan_kernel_v4 carries at pitch 768.
 // 4 pairs = 192 queries per workgroup: one A fragment feeds THREE MFMAs (a third less LDS read per flop as well), a block is
 // 3072 MFMA cycles per SIMD, the fill needed drops to 21 B/clk/CU and the ring's latency budget grows by half.
@@ -14,7 +14,7 @@
 //   * class words: ONE copy per pair in LDS (1.5 KiB = 48 queries x 8 words; the role-0 wave refreshes it, both read it: a
 //     stale word is merely a weaker bound), which is what lets ring + copies + exchange slots fit 160 KiB;
 //   * query tiles are 192 wide: the host pads the staged queries / insert bounds / lists to whole tiles (mips_hip.hip).
-// Everything else -- ring, exchange of the foreign half's partial sums through LDS, split block barrier -- is scan_kernel_ks's.
+// Ring and split block barrier are scan_kernel_v4's; the foreign half's partial sums are exchanged through LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,7 +28,9 @@ namespace mips {
 // PUB: every sub-list publishes (vouches for) its PUB-th best entry, so the 8 class words of a query stand for 8 PUB documents:
 // the pool selected from the lists may be 8 PUB deep (8 / 16 / 32 candidates: mips_hip.hip, "optimistic" pools and the first
 // stage of the fp32-exact search at row pitch 1024), as scan_kernel_v4's PUB.
-template <int KL, int KS32, int AD, int TIMING_MODE = 0, int PUB = 1>
+// (the fourth slot held a diagnostic axis, retired; it stays in the parameter list so that the instance names remain the ones
+// profiles/, latest_traffic.json and the tests know)
+template <int KL, int KS32, int AD, int = 0, int PUB = 1>
 __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
     static_assert(PUB >= 1 && PUB <= KL, "a sub-list vouches for one of its own entries");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -59,12 +61,6 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
     const int qt = (xcd % p.qgroups) + p.qgroups * (j0 % p.qt_per_group);
     const int split = (xcd / p.qgroups) * p.splits_per_group + j0 / p.qt_per_group;
     if (qt >= p.nqt) return;
-    const bool pf_leader = (j0 % p.qt_per_group) == 0;
-    // TIMING_MODE 10 (diagnostic, same results): shader-clock cycles this wave spends in the DMA wait of its arrival, in the block
-    // barrier's poll and in the pair's poll, summed over the launch into the five words p.nq_dev points at (the launcher passes a
-    // scratch buffer there: tools/ab.py prints them)
-    unsigned long long t_vm = 0ull, t_bar = 0ull, t_pair = 0ull;
-    const unsigned long long t_start = TIMING_MODE == 10 ? __builtin_readcyclecounter() : 0ull;
     if (p.spin_limit < 0 && tid == 0) *p.err = 1u; // test-only: force the scan-error path (include/mips_hip.h, "spin_limit")
     const bool idle_pair = (qt * TN + pair * 16 * NCB) >= p.nq; // all 48 queries of the pair are padding (scan_kernel_v3.hpp)
 
@@ -105,9 +101,7 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
     constexpr unsigned XCH_AREA = THR_AREA + PAIRS * THR_PAIR;
     constexpr unsigned XCH_WAVE = NCB * 1024u;
     constexpr unsigned CNT_AREA = XCH_AREA + WAVES * XCH_WAVE;
-    constexpr unsigned PF_AREA = CNT_AREA + 64;     // 256 B nobody reads: where the L2 prefetch of a later block lands
-    constexpr bool PREFETCH = TIMING_MODE == 7 || TIMING_MODE == 8 || TIMING_MODE == 9;
-    static_assert(PF_AREA + 256 <= 160 * 1024, "LDS budget");
+    static_assert(CNT_AREA + 64 + 256 <= 160 * 1024, "LDS budget"); // (+ 256 B nobody uses: the launch's byte count, kept as measured)
     // p.gthr = [query tile][pair][48 queries][8 words]: both waves of a pair publish into the same 1.5 KiB
     const __amdgpu_buffer_rsrc_t thr_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(reinterpret_cast<unsigned char*>(p.gthr) + (int64_t)qt * (PAIRS * THR_PAIR)), 0, PAIRS * THR_PAIR, 0x00020000);
@@ -160,25 +154,9 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
             asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, 1\n\tds_add_u32 %0, %1" : "=&v"(ta), "=&v"(tb) : "s"(saddr) : "memory");
 #endif
     };
-    auto arrive = [&](bool in_loop = true) {
-        // 2-stage ring: this wave's share of the NEXT block has landed (the one younger operation that may still be in flight is
-        // the block's L2 prefetch, issued after the pieces)
-        const unsigned long long t0 = TIMING_MODE == 10 ? __builtin_readcyclecounter() : 0ull;
-        if (PREFETCH && in_loop) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (TIMING_MODE == 10) t_vm += __builtin_readcyclecounter() - t0;
+    auto arrive = [&]() { // 2-stage ring: this wave's share of the NEXT block has landed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         bump(cnt_lds);
-    };
-    // One dword of each 128-B line of a block PF_DIST blocks ahead, 64 lines per wave, into the dummy area: the L2 miss of that
-    // line is taken here, 2+ blocks before its DMA piece is issued, instead of inside the 2-stage ring's one-block window.
-    constexpr int PF_DIST = TIMING_MODE == 8 ? 6 : 3;
-    auto prefetch_block = [&](const unsigned char* blk_base) {
-        const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc((void*)blk_base, 0, (int)(V3_DB * row_bytes), 0x00020000);
-        // TIMING_MODE 9: only ONE of the workgroups that share a document stream (the first query tile of its XCD group) touches
-        // memory; the others issue the same operation out of range (no access, zeros into the dummy area; uniform vmcnt arithmetic)
-        const unsigned voff = (TIMING_MODE != 9 || pf_leader) ? lane_id_here() * 128u : (0x40000000u | (lane_id_here() * 4u));
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(smem + PF_AREA), 4, voff, wave * 8192, 0, 0);
     };
     auto poll = [&](unsigned addr, unsigned need) {
         for (int spin = 0;; ++spin) {
@@ -197,12 +175,6 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
 
     // epilogue of the OWNED 16-document half (scan_kernel_v4's): acc[n] = documents base .. base + 3 vs query 16 n + c
     auto epilogue_half = [&](f32x4 (&acc)[NCB], int blk) {
-        if (TIMING_MODE == 1) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" ::"v"(acc[0]), "v"(acc[1]), "v"(acc[2]));
-#endif
-            return;
-        }
         const float mx0 = fmaxf(fmaxf(acc[0][0], acc[0][1]), fmaxf(acc[0][2], acc[0][3]));
         const float mx1 = fmaxf(fmaxf(acc[1][0], acc[1][1]), fmaxf(acc[1][2], acc[1][3]));
         const float mx2 = fmaxf(fmaxf(acc[2][0], acc[2][1]), fmaxf(acc[2][2], acc[2][3]));
@@ -228,13 +200,12 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
         }
     };
 
-    auto block = [&](bool refresh, int blk, int stage, const unsigned char* nbase, int nstage, const unsigned char* pbase) {
+    auto block = [&](bool refresh, int blk, int stage, const unsigned char* nbase, int nstage) {
         // pieces of the NEXT block first: their stage was released by the barrier just passed
         if (refresh) refresh_thresholds();
         if (idle_pair) {
 #pragma unroll
             for (int i = 0; i < PPW; ++i) issue_piece(nbase, nstage, i);
-            if (PREFETCH) prefetch_block(pbase);
             arrive();
             return;
         }
@@ -265,22 +236,11 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
                 if (t + AD < CHAIN) ar[t % AD] = lds_frag(t + AD);
                 // The pieces of the next block: early (they must have landed by the end of this block), but NOT by both waves of a
                 // SIMD at once -- the two partners (waves w and w + 4) pass the barrier together, and a piece costs its wave 100+ cycles
-                // of issue that only the partner's MFMAs can cover (the diagnostic build without the DMA, TIMING_MODE 2, runs 17 %
-                // faster: profiles/r3_pitch1024).  One piece every other step of the foreign half, the partners on alternate steps.
+                // of issue that only the partner's MFMAs can cover (a diagnostic build without the DMA ran 17 % faster:
+                // profiles/r3_pitch1024).  One piece every other step of the foreign half, the partners on alternate steps.
                 // The pieces are issued UNCONDITIONALLY (the last block re-fetches itself, see the main loop): with a second branch
                 // per site the 256-VGPR allocation spills a query fragment and reloads it in every block.
-                // TIMING_MODE 4 / 5 / 6 (diagnostics, same results): every wave in steps 0 .. PPW - 1 (the first build) / waves
-                // 0 .. 3 in steps 0 .. PPW - 1 and waves 4 .. 7 in steps PPW .. 2 PPW - 1 / every wave on the even steps.
-                if (PREFETCH && hpos == 1 && j == 0) prefetch_block(pbase);
-                if (TIMING_MODE == 4) {
-                    if (hpos == 0 && j < PPW) issue_piece(nbase, nstage, j);
-                } else if (TIMING_MODE == 5) {
-                    if (hpos == 0 && j < 2 * PPW && (j / PPW) == (wave >> 2)) issue_piece(nbase, nstage, j % PPW);
-                } else if (TIMING_MODE == 6) {
-                    if (hpos == 0 && j < 2 * PPW && (j & 1) == 0) issue_piece(nbase, nstage, j >> 1);
-                } else if (TIMING_MODE != 2) {
-                    if (hpos == 0 && j < 2 * PPW && ((j ^ (wave >> 2)) & 1) == 0) issue_piece(nbase, nstage, j >> 1); // (this spelling allocates without a spill: tools/kernel_regs.py)
-                }
+                if (hpos == 0 && j < 2 * PPW && ((j ^ (wave >> 2)) & 1) == 0) issue_piece(nbase, nstage, j >> 1); // (this spelling allocates without a spill: tools/kernel_regs.py)
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (hpos == 0) {
@@ -289,15 +249,11 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
                 unsigned char* slot = smem + XCH_AREA + wave * XCH_WAVE + lane_id_here() * 16u;
 #pragma unroll
                 for (int n = 0; n < NCB; ++n) *reinterpret_cast<f32x4*>(slot + 1024 * n) = acc[0][n];
-                if (TIMING_MODE != 3) bump(xcnt_mine); // (TIMING_MODE 3: diagnostic build without the pair's counter hand-shake)
+                bump(xcnt_mine);
             }
         }
         // the partner's partial sums for MY half
-        {
-            const unsigned long long t0 = TIMING_MODE == 10 ? __builtin_readcyclecounter() : 0ull;
-            if (TIMING_MODE != 3) poll(xcnt_partner, (unsigned)(blk - b0) + 1u);
-            if (TIMING_MODE == 10) t_pair += __builtin_readcyclecounter() - t0;
-        }
+        poll(xcnt_partner, (unsigned)(blk - b0) + 1u);
         f32x4 own[NCB];
         {
             const unsigned char* slot = smem + XCH_AREA + (wave ^ 1) * XCH_WAVE + lane_id_here() * 16u;
@@ -305,7 +261,7 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
             for (int n = 0; n < NCB; ++n) own[n] = acc[1][n] + *reinterpret_cast<const f32x4*>(slot + 1024 * n); // (own K half) + (the partner's)
         }
         arrive(); // chain done, the partner's slot read, this wave's share of the next block landed
-        if (refresh && TIMING_MODE == 0) {
+        if (refresh) {
             // minimum of the 8 class words of queries c, 16 + c and 32 + c (what an earlier refresh of the pair's copy brought, or 0)
             const unsigned a0 = (unsigned)(size_t)(lds_void*)smem + THR_AREA + pair * THR_PAIR + (lane_id_here() & 15u) * 32u;
 #pragma unroll
@@ -341,30 +297,16 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_k3(ScanArgs p) {
         for (int i = 0; i < PPW; ++i) issue_piece(first, 0, i);
     }
     __syncthreads();
-    if (nb > 0) arrive(false); // this wave's share of block 0 has landed
+    if (nb > 0) arrive(); // this wave's share of block 0 has landed
     for (int i = 0; i < nb; ++i) {
         arrivals_needed += WAVES;
-        {
-            const unsigned long long t0 = TIMING_MODE == 10 ? __builtin_readcyclecounter() : 0ull;
-            poll(cnt_lds, arrivals_needed); // every share of block i landed; everyone is done with block i - 1
-            if (TIMING_MODE == 10) t_bar += __builtin_readcyclecounter() - t0;
-        }
+        poll(cnt_lds, arrivals_needed); // every share of block i landed; everyone is done with block i - 1
         // (the last block of the range re-fetches ITSELF into the free stage instead of a next block: the pieces are issued
         // unconditionally, the MFMA chain stays one basic block)
         const unsigned char* nbase = first + (int64_t)(i + 1 < nb ? i + 1 : i) * blk_bytes;
-        const int ipf = i + PF_DIST < nb ? i + PF_DIST : nb - 1;
-        block(i < 8 || (i & 7) == 0, b0 + i, i & 1, nbase, (i + 1) & 1, first + (int64_t)ipf * blk_bytes);
+        block(i < 8 || (i & 7) == 0, b0 + i, i & 1, nbase, (i + 1) & 1);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (TIMING_MODE == 10 && p.nq_dev != nullptr && lane_id_here() == 0u && !idle_pair) {
-        unsigned long long* dbg = reinterpret_cast<unsigned long long*>(const_cast<int*>(p.nq_dev));
-        atomicAdd(dbg + 0, t_vm);
-        atomicAdd(dbg + 1, t_bar);
-        atomicAdd(dbg + 2, t_pair);
-        atomicAdd(dbg + 3, (unsigned long long)(__builtin_readcyclecounter() - t_start));
-        atomicAdd(dbg + 4, (unsigned long long)nb);
-        atomicAdd(dbg + 5, 1ull);
-    }
 
     // lists: [q][nsplit][8 = 2 document halves x 4 lane groups][KL]
 #pragma unroll

@@ -16,7 +16,7 @@
 //     document of global rank r can only be pushed out of its sub-list by KL better documents of the same
 //     sub-list, so ranks 1 .. KL survive for certain (KL = 6 = k + 1 for k <= 5), the re-score pool is the
 //     8 best of the union;
-//   * shared insert bounds as scan_kernel_v3 TMODE 2: every sub-list publishes its best score (PUB = 1; its PUB-th best
+//   * shared insert bounds as scan_kernel_v3's class words: every sub-list publishes its best score (PUB = 1; its PUB-th best
 //     in general) into class word (4 split + g) & 7 of its query, the bound is the minimum of the 8 words, re-read
 //     sparsely: 8 PUB distinct documents score at least the bound, so nothing below it belongs to a pool of 8 PUB.
 //     PUB = 4 serves the "optimistic" pools of 32 (mips_hip.hip): the lists still keep 6 entries each, the margin
@@ -44,7 +44,9 @@ __device__ __forceinline__ unsigned lane_id_here() {
 }
 
 // NT_DOCS: non-temporal document DMA -- for searches of ONE query tile, where every document block has a single reader
-template <int KL, int KS32, int AD, int TIMING_MODE = 0, bool NT_DOCS = false, int PUB = 1>
+// (the fourth slot held a diagnostic axis, retired; it stays in the parameter list so that the instance names remain the ones
+// profiles/, latest_traffic.json and the tests know)
+template <int KL, int KS32, int AD, int = 0, bool NT_DOCS = false, int PUB = 1>
 __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int WAVES = 8;
@@ -71,10 +73,6 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     if (qt >= p.nqt) return;
     if (p.spin_limit < 0 && tid == 0) *p.err = 1u; // test-only: force the scan-error path (include/mips_hip.h, "spin_limit")
     const bool idle_wave = (qt * TN + wave * 32) >= p.nq;
-    // experiments (profiles/r3_v4_prio; results unchanged): TIMING_MODE 3 / 5 = static priority for the younger half of the
-    // workgroup (waves 4 .. 7 lose every issue arbitration against their SIMD partners 0 .. 3: MI355X_MICROARCH.md, "Two waves per
-    // SIMD", item 4); 4 / 5 = the arrival poll spins on s_nop instead of s_sleep 1 (64-cycle wake-up granularity)
-    if ((TIMING_MODE == 3 || TIMING_MODE == 5) && wave >= 4) __builtin_amdgcn_s_setprio(1);
 
     const int b0 = split * p.tiles_per_split;
     int b1 = b0 + p.tiles_per_split;
@@ -107,7 +105,7 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
         }
     }
 
-    // ---- shared insert bounds (scan_kernel_v3.hpp, TMODE 2): p.gthr = [query tile][wave][32 queries][8 words]
+    // ---- shared insert bounds (scan_kernel_v3.hpp, "shared per-query thresholds"): p.gthr = [query tile][wave][32 queries][8 words]
     constexpr unsigned THR_AREA = STAGES * STAGE_BYTES;
     constexpr unsigned THR_WAVE = 1024u;
     constexpr unsigned DUMP_AREA = THR_AREA + WAVES * THR_WAVE;
@@ -127,29 +125,15 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     // ---- LDS-DMA map (as v3): piece pc = slab * 4 + rg, 8 rows x 128 B
     const unsigned char* docs_b = reinterpret_cast<const unsigned char*>(p.docs);
     const int64_t row_bytes = (int64_t)p.ld * 2;
-    // TIMING_MODE 14 (experiment, same results): the per-lane source offset lives in ONE register for the whole kernel instead of
-    // being re-derived from the lane id for every piece (~10 vector instructions each, 6 pieces per block and wave)
-    unsigned lane_off_kept = 0u;
-    if (TIMING_MODE == 14) {
-        const unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        lane_off_kept = (ln >> 3) * (unsigned)row_bytes + (((ln & 7u) ^ ((ln >> 4) & 7u)) << 4);
-#if defined(__HIP_DEVICE_COMPILE__)
-        asm volatile("" : "+v"(lane_off_kept));
-#endif
-    }
     auto issue_piece = [&](const unsigned char* blk_base, int stage, int i) {
-        if (TIMING_MODE == 6 || TIMING_MODE == 8) return; // diagnostic builds (results are wrong): the ring is never filled
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc((void*)blk_base, 0, (int)(V3_DB * row_bytes), 0x00020000);
         const int pc = wave + WAVES * i;
         const int slab = pc >> 2, rg = pc & 3;
         // per-lane source offset, recomputed per piece from the lane id (the kernel has no VGPR to spare):
         // row lane >> 3 of the piece, chunk slot (lane & 7) ^ ((row >> 1) & 7) = (lane & 7) ^ ((4 rg + (lane >> 4)) & 7)
-        unsigned lane_off0 = lane_off_kept;
-        if (TIMING_MODE != 14) {
-            const unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            lane_off0 = (ln >> 3) * (unsigned)row_bytes + (((ln & 7u) ^ ((ln >> 4) & 7u)) << 4);
-        }
+        const unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const unsigned lane_off0 = (ln >> 3) * (unsigned)row_bytes + (((ln & 7u) ^ ((ln >> 4) & 7u)) << 4);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(smem + stage * STAGE_BYTES + pc * 1024), 16,
                                                  (rg & 1) ? (lane_off0 ^ 64u) : lane_off0,
                                                  rg * 8 * (int)row_bytes + slab * 128, 0, NT_DOCS ? 2 : 0);
@@ -169,23 +153,14 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     const unsigned cnt_lds = (unsigned)(size_t)(lds_void*)(smem + DUMP_AREA + 1024);
     unsigned arrivals_needed = 0;
     constexpr int PER_BLOCK = PPW + 1;
-    // TIMING_MODE 15 (diagnostic, same results): shader-clock cycles this wave spends in the DMA wait of its arrival and in the
-    // block barrier's poll, summed over the launch into the words p.nq_dev points at (the launcher passes a scratch buffer there)
-    // (32-bit sums of low words pinned to SGPRs: the kernel has no vector register for them)
-    auto clk = [&]() { return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)__builtin_readcyclecounter()); };
-    unsigned t_vm = 0u, t_bar = 0u;
-    const unsigned t_start = TIMING_MODE == 15 ? clk() : 0u;
     auto arrive = [&]() {
-        const unsigned t0 = TIMING_MODE == 15 ? clk() : 0u;
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 2) * PER_BLOCK) : "memory");
-        if (TIMING_MODE == 15) t_vm += clk() - t0;
 #if defined(__HIP_DEVICE_COMPILE__)
         if (lane == 0) asm volatile("ds_add_u32 %0, %1" ::"v"(cnt_lds), "v"(1u) : "memory");
 #endif
     };
     auto wait_all = [&]() {
         arrivals_needed += WAVES;
-        if (TIMING_MODE == 7) return; // diagnostic build (results are wrong): nobody waits for the block's arrivals
         for (int spin = 0;; ++spin) {
             unsigned v = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -196,13 +171,7 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
                 if (lane == 0) *p.err = 1u;
                 break;
             }
-            if (TIMING_MODE == 4 || TIMING_MODE == 5) {
-#if defined(__HIP_DEVICE_COMPILE__)
-                asm volatile("s_nop 15" ::: "memory");
-#endif
-            } else {
-                __builtin_amdgcn_s_sleep(1);
-            }
+            __builtin_amdgcn_s_sleep(1);
         }
     };
 
@@ -210,12 +179,6 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     // against queries c (n = 0) and 16 + c (n = 1).  No synchronisation in here: at mid-block the partner
     // wave's MFMAs keep the matrix pipe busy while this wave runs the few instructions of the pre-test.
     auto epilogue_half = [&](f32x4 (&acc)[2], int blk, int half) {
-        if (TIMING_MODE == 1 || TIMING_MODE == 8) { // diagnostic builds (results are wrong): no epilogue at all
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("" ::"v"(acc[0]), "v"(acc[1]));
-#endif
-            return;
-        }
         // fast path: 6 max, 2 compares, one branch -- everything else is derived only if a document passes
         const float mx0 = fmaxf(fmaxf(acc[0][0], acc[0][1]), fmaxf(acc[0][2], acc[0][3]));
         const float mx1 = fmaxf(fmaxf(acc[1][0], acc[1][1]), fmaxf(acc[1][2], acc[1][3]));
@@ -275,14 +238,11 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
                 acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ar[t % AD], bq[0][s], acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ar[t % AD], bq[1][s], acc[1], 0, 0, 0);
                 if (t + AD < STEPS) ar[t % AD] = lds_frag(t + AD);
-                // TIMING_MODE 9 (experiment, same results): the two waves of a SIMD (w, w + 4) issue their pieces half a period apart
-                if (TIMING_MODE == 9) {
-                    if ((t % (STEPS / PPW)) == ((STEPS / PPW) / 2) * (1 - (wave >> 2))) issue_piece(pbase, pstage, t / (STEPS / PPW));
-                } else if ((t % (STEPS / PPW)) == (STEPS / PPW) / 2) issue_piece(pbase, pstage, t / (STEPS / PPW));
+                if ((t % (STEPS / PPW)) == (STEPS / PPW) / 2) issue_piece(pbase, pstage, t / (STEPS / PPW));
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (half == 1) arrive(); // all LDS reads of this block are done; the epilogue runs un-synchronised
-            if (half == 1 && refresh && TIMING_MODE != 1 && TIMING_MODE != 8) {
+            if (half == 1 && refresh) {
                 // minimum of the 8 class words of queries c and 16 + c (what an earlier block's DMA brought, or 0);
                 // inline asm, one query at a time: see scan_kernel_v3.hpp
                 const unsigned thr_addr = thr_addr_of(lane_id_here());
@@ -332,29 +292,13 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     __syncthreads();
     if (nb > 0) arrive();
     for (int i = 0; i < nb; ++i) {
-        {
-            const unsigned t0 = TIMING_MODE == 15 ? clk() : 0u;
-            wait_all();
-            if (TIMING_MODE == 15) t_bar += clk() - t0;
-        }
-        // TIMING_MODE 10 / 11 / 12 (experiment, same results): the second wave of each SIMD starts its block 64 / 128 / 192 cycles
-        // late, so that the two waves' epilogues (an MFMA -> VALU dependency stall + ~10 dependent instructions per half, which both
-        // reach at the same moment when they leave the barrier together) fall into each other's MFMA chains
-        if (TIMING_MODE >= 10 && TIMING_MODE <= 12 && wave >= 4) __builtin_amdgcn_s_sleep(TIMING_MODE - 9);
+        wait_all();
         block(i < 8 || (i & 7) == 0, b0 + i, stage, pbase, pstage); // refresh schedule: scan_kernel_v3.hpp
         if (i + AHEAD + 1 < nb) pbase += blk_bytes;
         stage = stage == STAGES - 1 ? 0 : stage + 1;
         pstage = pstage == STAGES - 1 ? 0 : pstage + 1;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (TIMING_MODE == 15 && p.nq_dev != nullptr && lane_id_here() == 0u && !idle_wave) {
-        unsigned long long* dbg = reinterpret_cast<unsigned long long*>(const_cast<int*>(p.nq_dev));
-        atomicAdd(dbg + 0, (unsigned long long)t_vm);
-        atomicAdd(dbg + 1, (unsigned long long)t_bar);
-        atomicAdd(dbg + 3, (unsigned long long)(clk() - t_start));
-        atomicAdd(dbg + 4, (unsigned long long)nb);
-        atomicAdd(dbg + 5, 1ull);
-    }
 
 #pragma unroll
     for (int n = 0; n < 2; ++n) {

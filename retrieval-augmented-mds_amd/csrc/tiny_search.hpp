@@ -67,9 +67,6 @@ struct TinyArgs {
     int* res_hit_n;        // [>= 16]
     unsigned* res_unres;
     void* q_out;           // [nq][ld] bf16 (pitch ld) or, F32, [nq][plane] float32
-#ifdef MIPS_EXPERIMENTAL
-    unsigned long long* dbg; // [gridDim.x][16] phase time stamps (100 MHz), or nullptr
-#endif
     MergeArgs m;           // part_s / part_i / ncand / ll / docs / ld / k / metric / phi / idx_offset / margin fields;
                            // qbuf, out_s, out_i are set by the kernel (LDS)
 };
@@ -98,17 +95,6 @@ constexpr int tiny_lds_bytes(int ld, int plane = 0) {
            + 16 * 8                    // |q|^2
            + 16 * 4 + 16;              // margin bounds of the queries, max |x|^2
 }
-
-#ifdef MIPS_EXPERIMENTAL
-#define TINY_STAMP(i)                                                                  \
-    do {                                                                               \
-        if (a.dbg && threadIdx.x == 0) a.dbg[blockIdx.x * 16 + (i)] = wall_clock64();  \
-    } while (0)
-#else
-#define TINY_STAMP(i) \
-    do {              \
-    } while (0)
-#endif
 
 // Cross-lane reductions on DPP (data-parallel primitives: a lane permutation folded into the VALU operand fetch, a few
 // cycles) instead of __shfl_xor (ds_bpermute_b32 through the LDS crossbar, ~100 cycles of latency each: six dependent
@@ -409,10 +395,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
     const int wave = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
     const int nwg = gridDim.x;
-    TINY_STAMP(0);
-#ifdef MIPS_EXPERIMENTAL
-    if (a.dbg && threadIdx.x == 0) a.dbg[blockIdx.x * 16 + 12] = clock64();
-#endif
 
     // ---- the first tile's documents: the whole K of the tile in flight, one memory round trip, issued before anything else
     const int ks128 = a.ld / 128; // 1 .. 8 groups of four 32-k steps
@@ -428,8 +410,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
                 for (int u = 4 * u4; u < 4 * u4 + 4; ++u) av[u] = *reinterpret_cast<const bf16x8*>(arow + 32 * u);
             }
     }
-
-    TINY_STAMP(1);
     double xm = 0.0, xres = 0.0;
     if (tid == 0 && a.m.nflag != nullptr) {
         xm = *a.m.xmax2; // (margin check: the load travels with the documents)
@@ -444,7 +424,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
         const int nz = (16 - a.nq) * a.ld / 2;
         for (int t = tid; t < nz; t += TINY_THREADS) z[t] = 0u;
     }
-    TINY_STAMP(2);
 #pragma unroll 1
     for (int r = wave; r < a.nq; r += TINY_WAVES) {
         const int nfull = a.d >> 6; // whole groups of 64 columns; the (d % 64) others are the "tail" group
@@ -488,13 +467,11 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
             for (int t = tt; t < a.plane; t += 64) qf[r * a.plane + t] = t < a.d ? xt * inv : 0.f;
         }
     }
-    TINY_STAMP(3);
     if (tid == 0) {
         xmax2_s[0] = xm;
         xmax2_s[1] = xres;
     }
     __syncthreads();
-    TINY_STAMP(4);
 
     // ---- phase 1: MFMA scores of this wave's 16-document tiles, running top-6 per lane
     float ls[TINY_KL];
@@ -532,7 +509,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
             if (sc > ls[TINY_KL - 1]) list_insert<TINY_KL>(ls, li, sc, base + r);
         }
     }
-    TINY_STAMP(5);
     // ---- first selection level, inside the workgroup: the 32 lane lists of a query (8 waves x 4 g) -> its 8 best
     {
         const int o = c * TINY_WL + (wave * 4 + g) * TINY_KL;
@@ -629,7 +605,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
             __builtin_amdgcn_wave_barrier();
         }
     }
-    TINY_STAMP(6);
     // ---- ticket: release this workgroup's candidates, find out whether it is the last one
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -640,7 +615,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
         is_last = t == gridDim.x - 1;
     }
     __syncthreads();
-    TINY_STAMP(7);
     if (!is_last) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); // every wave of the last workgroup reads other workgroups' candidates
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -738,7 +712,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
         }
     }
     __syncthreads();
-    TINY_STAMP(8);
     // exact re-score: 8 lanes per (query, candidate) pair, 64 pairs per round
     if (F32) { // on the fp32 rows (tiny_seq_dot_f32); L2 also needs the canonical |q|^2: nq more "pairs" (q, q)
         const int npair = a.nq * TINY_POOL + (L2 ? a.nq : 0);
@@ -801,7 +774,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
         }
     }
     __syncthreads();
-    TINY_STAMP(9);
     // rank, margin check, write: one lane per pair, 8 queries per wave; the k results go to LDS [q][m.k]
     if (wave < 2) {
         const int64_t q = wave * 8 + lane / TINY_POOL;
@@ -814,7 +786,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
         rank_flag_write<TINY_POOL, L2>(m, q, slot, inq, ci, valid, dot, qq, lane);
     }
     __syncthreads();
-    TINY_STAMP(10);
     // hand-off to the stream-ordered exact pass (resolve_kernels.hpp): what compact_flags_kernel does for the general path, and
     // -- only when a query was flagged -- the staged queries in global memory, where exact_filter_kernel reads them
     if (a.res_cnt != nullptr) {
@@ -859,10 +830,6 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
             ++w;
         }
     }
-    TINY_STAMP(11);
-#ifdef MIPS_EXPERIMENTAL
-    if (a.dbg && threadIdx.x == 0) a.dbg[blockIdx.x * 16 + 13] = clock64();
-#endif
 }
 
 } // namespace mips

@@ -1090,7 +1090,7 @@ def test_experimental_scan_variants_are_bit_identical():
             ix.set_param(name, params.get(name, 0))
         s, i = ix.search(q, k)
         assert torch.equal(i, ref_i) and torch.equal(s, ref_s), params
-    # the experimental `sub` instances (two of them wrong by design) are not in the shipped library
+    # the experimental `sub` instances (several of them wrong by design) went with the retired A/B library
     with pytest.raises(RuntimeError, match="experimental"):
         ix.set_param("sub", 8)
     ix.set_param("sub", 0)
@@ -1779,8 +1779,8 @@ def test_pitch_1024_k_split_kernel_is_bit_identical():
     """Row pitch 1024: scan_kernel_v3's one-wave-per-SIMD configuration ("variant" = 3; the default up to 256 queries) and
     scan_kernel_k3 ("variant" = 7, the default beyond 256 queries: wave pairs split K, partial sums meet in LDS, 48 queries per
     pair, 192-query tiles, sub-lists of 4) return the same bits -- and the oracle's -- on ragged sizes, single- and multi-tile
-    query counts, forced split counts, ties.  (scan_kernel_ks, "variant" = 6, the first K-split kernel, lives in the A/B library
-    of tools/ab.py only; the shipped library ignores the value and the default kernels answer.)"""
+    query counts, forced split counts, ties.  (scan_kernel_ks, "variant" = 6, the first K-split kernel, went with the retired A/B
+    library; the shipped library ignores the value and the default kernels answer.)"""
     for n, nq, d, k in ((70001, 300, 1024, 5), (150001, 700, 1000, 5), (64 * 37 + 5, 129, 800, 4), (5000, 40, 1024, 1), (40000, 193, 1024, 5)):
         ix = ram.MipsIndex(d)
         ix.add_synthetic(n, row0=0, seed=171, kind=synth.KIND_GAUSS)

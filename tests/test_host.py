@@ -409,8 +409,8 @@ def test_faiss_shim_surface_without_a_gpu(tmp_path, monkeypatch):
 def test_no_shipped_kernel_spills_or_uses_scratch():
     """Every gfx950 kernel of the built library allocates without a spill and without a private segment (a scratch reload
     behind LDS-DMA pieces drains the ring: the register budgets of the scan kernels are set to the last VGPR, and a small edit
-    can tip one over -- tools/kernel_regs.py reads the code object's notes, no GPU needed), and the kernels that only exist for
-    A/B measurements (`sub` instances, scan_kernel_v5 / scan_kernel_ks) are not in the shipped library."""
+    can tip one over -- tools/kernel_regs.py reads the code object's notes, no GPU needed), and the kernels that only existed for
+    A/B measurements (`sub` instances, scan_kernel_v5 / scan_kernel_ks: retired) are not in the shipped library."""
     import sys
 
     ram.build()

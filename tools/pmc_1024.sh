@@ -1,8 +1,10 @@
 #!/bin/bash
 # PMC counters of the pitch-1024 scan kernels (GPU box): one rocprofv3 --pmc pass per counter group, never combined with a trace domain.
 # usage: tools/pmc_1024.sh <out-dir under gpurun_out> <variant>
+# variant: 0 automatic, 3 scan_kernel_v3 (128 queries per workgroup), 7 scan_kernel_k3 (192) -- the kernels that exist at this pitch
 set -o pipefail
 OUT=gpurun_out/$1; V=$2
+case "$V" in 0|3|7) ;; *) echo "pmc_1024.sh: variant must be 0, 3 or 7 (got '$V')" >&2; exit 2;; esac
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 i=0
