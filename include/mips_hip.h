@@ -185,8 +185,9 @@ int mips_search_split(mips_index_t* index, const void* q, int q_dtype, int64_t n
  * recall@100 / @1000 evaluation and hard-negative mining.  Arguments and results as mips_search (same canonical score, same order
  * and tie rule, same padding; for k <= MIPS_MAX_K the output equals mips_search bit for bit).  Served: bf16 and fp32-exact
  * indexes of at most 1024 columns, both metrics, F32 / BF16 queries in host or device memory, MIPS_FORCE_IP, MIPS_Q_DEVICE,
- * MIPS_OUT_DEVICE, idx_offset.  MIPS_E_UNSUPPORTED: k > MIPS_MAX_K_WIDE, e4m3 storage, MIPS_OUT_PACKED, rows of more than 1024
- * columns.
+ * MIPS_OUT_DEVICE, MIPS_OUT_PACKED (with MIPS_OUT_DEVICE; out_scores may be NULL, as in mips_search: a packed row equals the
+ * plain result bit for bit, padding included), idx_offset.  MIPS_E_UNSUPPORTED: k > MIPS_MAX_K_WIDE, e4m3 storage, rows of more
+ * than 1024 columns.
  * How: the index is walked in row chunks; a threshold scan (bf16 MFMA; the bf16 image of an fp32-exact index) appends every row
  * scoring above the query's threshold to that query's candidate segments, a select keeps the best k' = k + slack per query and
  * raises the threshold, the k' survivors are re-scored canonically and ranked (DESIGN.md "Wide top-k").  EVERY wide search is
@@ -228,6 +229,18 @@ int mips_merge_topk(const float* cand_s, const int64_t* cand_i, int64_t nq, int 
  * gathered = DEVICE [parts, nq, k, 2] int64 (rank-major). */
 int mips_merge_topk_packed(const int64_t* gathered, int64_t nq, int parts, int k, int metric,
                            float* out_s, int64_t* out_i, int device, void* hip_stream);
+
+/* The merge for wide lists (k up to MIPS_MAX_K_WIDE; parts * k <= 65536), same payload, same result: gathered = DEVICE
+ * [parts, nq, k, 2] int64 (rank-major).  PRECONDITION: each part's k entries are in result order -- score descending (L2:
+ * ascending), then id ascending, padding (id < 0) last -- which is what mips_search and mips_search_wide emit.  Entries are
+ * ordered by (score; id, id < 0 taken as INT64_MAX; part; position), so ranks are a permutation even among padding and the
+ * output equals mips_merge_topk_packed on the same payload bit for bit.  One workgroup per query: a candidate's rank is its
+ * own position plus, per other part, a binary search for the number of entries ordering before it -- O(parts k parts log k)
+ * comparisons per query where the counting merge spends (parts k)^2.  The query's lists are staged in LDS while parts * k * 16
+ * bytes is at most 128 KiB; larger merges search the payload in global memory.  One MIPS_IDX_POISON id poisons the whole
+ * output row. */
+int mips_merge_topk_sorted_packed(const int64_t* gathered, int64_t nq, int parts, int k, int metric,
+                                  float* out_s, int64_t* out_i, int device, void* hip_stream);
 
 /* The ignore filter of Mips.search (sotasum/mips.py:388-398) on the device: from k_fetched (= k + 1)
  * hits per query drop every hit whose id equals ignore[q] and keep the first k.  All DEVICE buffers:

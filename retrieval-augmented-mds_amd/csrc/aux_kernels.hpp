@@ -799,6 +799,85 @@ __global__ __launch_bounds__(64) void merge_topk_packed_kernel(const int64_t* ga
     }
 }
 
+// Merge of SORTED lists (the wide top-k, k up to MIPS_MAX_K_WIDE): gathered [parts][nq][k][2] int64 as above, each part's k
+// entries in result order (score descending -- L2: ascending --, then id ascending, padding id < 0 last).  One workgroup per
+// query, one thread per candidate in strides.  Total order: (score in rank order; id, id < 0 as INT64_MAX; part; position) --
+// what merge_topk_packed_kernel counts by, so the two agree bit for bit.  A candidate's rank is its own position plus, for
+// every other part, the number of that part's entries ordering before it: the predicate is monotone along a sorted part, so
+// a binary search finds the count.  No sort, no atomics, O(c parts log k) comparisons instead of c^2.  The search in a part
+// stops at k - (rank so far): a count that reaches it puts the candidate past the k-th place whatever the true count is.
+// STAGE: the query's lists are copied to LDS first (12 bytes per entry: raw id, rank key); otherwise the searches read the
+// payload in global memory (it is L2-resident: c * 16 bytes per query).
+template <bool STAGE>
+__global__ __launch_bounds__(1024) void merge_topk_sorted_packed_kernel(const int64_t* gathered, int64_t nq, int parts, int k,
+                                                                        int metric, float* out_s, int64_t* out_i) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char merge_lds[];
+    int64_t* lds_id = reinterpret_cast<int64_t*>(merge_lds); // [c] raw ids
+    const int64_t q = blockIdx.x;
+    const int c = parts * k;
+    float* lds_key = reinterpret_cast<float*>(lds_id + c);   // [c] rank keys (L2: negated distances)
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const bool l2 = metric == 1;
+    auto entry = [&](int a) { return gathered + (((size_t)(a / k) * nq + q) * k + a % k) * 2; };
+    auto key_of = [&](int a) {
+        if (STAGE) return lds_key[a];
+        const float f = __uint_as_float((unsigned)entry(a)[0]);
+        return l2 ? -f : f;
+    };
+    auto id_of = [&](int a) { return STAGE ? lds_id[a] : entry(a)[1]; };
+    bool bad = false; // a shard handed over poisoned results: the merged row is poisoned too
+    for (int a = tid; a < c; a += nt) {
+        const int64_t* e = entry(a);
+        const int64_t id = e[1];
+        bad |= id == IDX_POISON;
+        if (STAGE) {
+            const float f = __uint_as_float((unsigned)e[0]);
+            lds_key[a] = l2 ? -f : f;
+            lds_id[a] = id;
+        }
+    }
+    if (__syncthreads_or(bad ? 1 : 0)) {
+        for (int t = tid; t < k; t += nt) {
+            out_s[(size_t)q * k + t] = poison_score();
+            out_i[(size_t)q * k + t] = IDX_POISON;
+        }
+        return;
+    }
+    // (odd strides run backwards: a thread that drew an early position -- long searches -- draws a late one -- leaves at once --
+    // in the next stride)
+    for (int a0 = 0, it = 0; a0 < c; a0 += nt, ++it) {
+        const int a = a0 + ((it & 1) ? nt - 1 - tid : tid);
+        if (a >= c) continue;
+        const int pa = a / k;
+        const float sa = key_of(a);
+        const int64_t raw = id_of(a);
+        const int64_t ia = raw < 0 ? INT64_MAX : raw;
+        int rank = a - pa * k;
+        for (int p = 0; p < parts && rank < k; ++p) {
+            if (p == pa) continue;
+            const int base = p * k;
+            int lo = 0, hi = k - rank;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                const float sb = key_of(base + mid);
+                bool before = sb > sa;
+                if (sb == sa) {
+                    const int64_t rb = id_of(base + mid);
+                    const int64_t ib = rb < 0 ? INT64_MAX : rb;
+                    before = ib < ia || (ib == ia && p < pa);
+                }
+                if (before) lo = mid + 1;
+                else hi = mid;
+            }
+            rank += lo;
+        }
+        if (rank < k) {
+            out_s[(size_t)q * k + rank] = l2 ? -sa : sa;
+            out_i[(size_t)q * k + rank] = raw;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ ignore filter of Mips.search on the device
 // sotasum/mips.py:388-398: k + 1 hits were fetched; per query drop every hit whose id equals ignore[q] and
 // keep the first k of the rest.  One thread per query (k1 <= 30).

@@ -27,7 +27,8 @@ struct WideScratch {
     unsigned* words; // [0] flagged queries of the call, [1] always 0 (unresolved)
 };
 
-int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, float* d_s, int64_t* d_i, int64_t idx_offset, bool q_dev,
+// packed: d_i is the MIPS_OUT_PACKED payload [nq][k][2] and d_s is not written (it may be NULL)
+int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool q_dev,
                 hipStream_t st) {
     const bool f32x = ix->plane > 0;
     const bool l2 = ix->call_metric == MIPS_METRIC_L2;
@@ -105,8 +106,9 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         const int64_t ns_pad = round_up(ns, mips::TN);
         const int nqt = (int)(ns_pad / mips::TN);
         const void* qs = (const char*)q + (size_t)s0 * ix->d * qesz;
-        float* out_s = d_s + (size_t)s0 * k;
-        int64_t* out_i = d_i + (size_t)s0 * k;
+        float* out_s = packed ? nullptr : d_s + (size_t)s0 * k;
+        int64_t* out_i = packed ? nullptr : d_i + (size_t)s0 * k;
+        int64_t* out_packed = packed ? d_i + (size_t)s0 * k * 2 : nullptr;
 
         // ---- stage the slice's queries: canonical form (bf16 rows / fp32 rows) and, fp32-exact index, bf16(q) for the scan
         const int64_t nq_padq = query_pad(ix, ns);
@@ -188,6 +190,7 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         ra.idx_offset = idx_offset;
         ra.out_s = out_s;
         ra.out_i = out_i;
+        ra.out_packed = out_packed;
         ra.flag = w.flag;
         ra.nflag = w.words;
         ra.qq = w.qq;
@@ -230,6 +233,7 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         xa.idx_offset = idx_offset;
         xa.out_s = out_s;
         xa.out_i = out_i;
+        xa.out_packed = out_packed;
         mips::WideSelArgs xe = se;
         xe.nseg = 1;
         xe.segcap = (int)xrows;

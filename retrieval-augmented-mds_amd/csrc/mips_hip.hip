@@ -506,12 +506,13 @@ int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, i
     if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_search_wide: negative nq or k");
     if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: k = %d exceeds MIPS_MAX_K_WIDE = %d", k, MIPS_MAX_K_WIDE);
     if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: e4m3 storage is not served (bf16 and fp32-exact indexes only)");
-    if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: no packed output");
     if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
         return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: stored rows of more than 1024 columns are not served");
     if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "mips_search_wide: q_dtype must be F32 or BF16");
     if (nq == 0 || k == 0) return MIPS_OK;
-    if (!q || !out_idx || !out_scores) return fail(MIPS_E_INVALID, "mips_search_wide: NULL buffer");
+    const bool packed = (flags & MIPS_OUT_PACKED) != 0;
+    if (packed && !(flags & MIPS_OUT_DEVICE)) return fail(MIPS_E_INVALID, "mips_search_wide: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE");
+    if (!q || !out_idx || (!out_scores && !packed)) return fail(MIPS_E_INVALID, "mips_search_wide: NULL buffer");
     if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: more than 2^24 queries in one call");
     DeviceGuard g(ix->device);
     hipStream_t st = (hipStream_t)hip_stream;
@@ -538,14 +539,14 @@ int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, i
     }
     if (ix->ntotal == 0) {
         const int64_t total = nq * k;
-        mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, nullptr, total, ix->call_metric);
+        mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, packed ? d_i : nullptr, total, ix->call_metric);
         HIP_TRY(hipGetLastError());
         ix->last_flagged = 0;
         ix->last_rescanned = 0;
         ix->last_unresolved = 0;
         ix->first_nflag_dev = nullptr;
     } else {
-        const int rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, idx_offset, (flags & MIPS_Q_DEVICE) != 0, st);
+        const int rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, st);
         if (rc) return rc;
     }
     if (!out_dev) {
@@ -647,6 +648,32 @@ int mips_merge_topk_packed(const int64_t* gathered, int64_t nq, int parts, int k
     DeviceGuard g(device);
     if (!g.ok) return fail(MIPS_E_HIP, "hipSetDevice(%d) failed", device);
     mips::merge_topk_packed_kernel<<<(int)nq, 64, 0, (hipStream_t)hip_stream>>>(gathered, nq, parts, k, metric, out_s, out_i);
+    HIP_TRY(hipGetLastError());
+    return MIPS_OK;
+}
+
+int mips_merge_topk_sorted_packed(const int64_t* gathered, int64_t nq, int parts, int k, int metric, float* out_s,
+                                  int64_t* out_i, int device, void* hip_stream) {
+    if (nq < 0 || parts <= 0 || k < 0) return fail(MIPS_E_INVALID, "mips_merge_topk_sorted_packed: bad sizes");
+    if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "mips_merge_topk_sorted_packed: k = %d exceeds MIPS_MAX_K_WIDE = %d", k, MIPS_MAX_K_WIDE);
+    if (nq == 0 || k == 0) return MIPS_OK;
+    if (!gathered || !out_s || !out_i) return fail(MIPS_E_INVALID, "mips_merge_topk_sorted_packed: NULL buffer");
+    if ((int64_t)parts * k > 65536) return fail(MIPS_E_UNSUPPORTED, "mips_merge_topk_sorted_packed: parts * k too large");
+    if (nq > INT32_MAX) return fail(MIPS_E_UNSUPPORTED, "mips_merge_topk_sorted_packed: more than 2^31 - 1 queries in one call");
+    DeviceGuard g(device);
+    if (!g.ok) return fail(MIPS_E_HIP, "hipSetDevice(%d) failed", device);
+    const int c = parts * k;
+    // one thread per candidate up to the largest workgroup; beyond that in strides
+    const int threads = c <= 64 ? 64 : c <= 128 ? 128 : c <= 256 ? 256 : c <= 512 ? 512 : 1024;
+    // the lists go to LDS while the payload of one query (16 bytes per entry) is at most 128 KiB of the CU's 160 KiB (8 x 1024:
+    // the staged form is 12 bytes per entry, 96 KiB); larger merges search the L2-resident payload
+    if ((size_t)c * 16 <= (128u << 10)) {
+        const int lds = c * 12;
+        HIP_TRY(hipFuncSetAttribute((const void*)mips::merge_topk_sorted_packed_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        mips::merge_topk_sorted_packed_kernel<true><<<(int)nq, threads, lds, (hipStream_t)hip_stream>>>(gathered, nq, parts, k, metric, out_s, out_i);
+    } else {
+        mips::merge_topk_sorted_packed_kernel<false><<<(int)nq, threads, 0, (hipStream_t)hip_stream>>>(gathered, nq, parts, k, metric, out_s, out_i);
+    }
     HIP_TRY(hipGetLastError());
     return MIPS_OK;
 }

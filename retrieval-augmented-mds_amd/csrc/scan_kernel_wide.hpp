@@ -302,6 +302,17 @@ __global__ void wide_init_kernel(int nq, int nq_pad, int* pool_n, wkey_t* tau_c,
 }
 
 // ------------------------------------------------------------------------------------------- exact re-score, rank, certificate
+// One result slot: the plain pair of arrays, or the packed all-gather payload [nq][k][2] = {float32 bits (zero-extended), id}.
+__device__ __forceinline__ void wide_write(float* out_s, int64_t* out_i, int64_t* out_packed, size_t o, float s, int64_t id) {
+    if (out_packed) {
+        out_packed[2 * o] = (int64_t)__float_as_uint(s);
+        out_packed[2 * o + 1] = id;
+    } else {
+        out_s[o] = s;
+        out_i[o] = id;
+    }
+}
+
 struct WideRescoreArgs {
     const wkey_t* pool;
     int pool_stride;
@@ -316,6 +327,7 @@ struct WideRescoreArgs {
     int64_t idx_offset;
     float* out_s;      // [nq][k]
     int64_t* out_i;
+    int64_t* out_packed; // or [nq][k][2] (MIPS_OUT_PACKED)
     unsigned char* flag; // [nq]
     unsigned* nflag;     // running count of flagged queries of the call
     double* qq;          // [nq] out: |q|^2 as the canonical sum
@@ -382,13 +394,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rescore_kernel(WideRescoreA
     __syncthreads();
     for (int i = tid; i < a.k; i += WIDE_THREADS) {
         const size_t o = (size_t)q * a.k + i;
-        if (i < n) {
-            a.out_s[o] = wide_dec<L2>(wide_hi(buf[i]));
-            a.out_i[o] = (int64_t)wide_row(buf[i]) + a.idx_offset;
-        } else {
-            a.out_s[o] = L2 ? INFINITY : -INFINITY;
-            a.out_i[o] = -1;
-        }
+        if (i < n) wide_write(a.out_s, a.out_i, a.out_packed, o, wide_dec<L2>(wide_hi(buf[i])), (int64_t)wide_row(buf[i]) + a.idx_offset);
+        else wide_write(a.out_s, a.out_i, a.out_packed, o, L2 ? INFINITY : -INFINITY, -1);
     }
     if (tid == 0) {
         // Certificate.  Every row outside the pool has an approximate score <= B = the score of the pool's worst member, so a
@@ -443,6 +450,7 @@ struct WideExactArgs {
     int64_t idx_offset;
     float* out_s;
     int64_t* out_i;
+    int64_t* out_packed;
 };
 
 // start of a round: empty pools; a row must reach the k-th result of the first pass to matter
@@ -524,13 +532,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_finalize_kernel(WideExactAr
     __syncthreads();
     for (int i = tid; i < a.k; i += WIDE_THREADS) {
         const size_t o = (size_t)q * a.k + i;
-        if (i < n) {
-            a.out_s[o] = wide_dec<L2>(wide_hi(buf[i]));
-            a.out_i[o] = (int64_t)wide_row(buf[i]) + a.idx_offset;
-        } else {
-            a.out_s[o] = L2 ? INFINITY : -INFINITY;
-            a.out_i[o] = -1;
-        }
+        if (i < n) wide_write(a.out_s, a.out_i, a.out_packed, o, wide_dec<L2>(wide_hi(buf[i])), (int64_t)wide_row(buf[i]) + a.idx_offset);
+        else wide_write(a.out_s, a.out_i, a.out_packed, o, L2 ? INFINITY : -INFINITY, -1);
     }
 }
 

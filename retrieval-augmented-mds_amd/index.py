@@ -30,8 +30,8 @@ def _stream_handle(device: int) -> int:
 
 
 def route_search(index, q, k: int, **kwargs):
-    """index.search(q, k), or index.search_wide(q, k) when k exceeds MAX_K and the index has a wide search (MipsIndex does;
-    ShardedMipsIndex and foreign duck-typed indexes keep their own search and its limits)."""
+    """index.search(q, k), or index.search_wide(q, k) when k exceeds MAX_K and the index has a wide search (MipsIndex and
+    ShardedMipsIndex do; foreign duck-typed indexes keep their own search and its limits)."""
     if int(k) > _lib.MAX_K and hasattr(index, "search_wide"):
         return index.search_wide(q, int(k), **kwargs)
     return index.search(q, k, **kwargs)
@@ -219,14 +219,7 @@ class MipsIndex:
         import torch
 
         k = int(k)
-        if k < 0:
-            raise ValueError("k must be >= 0")
-        if k > _lib.MAX_K_WIDE:
-            raise NotImplementedError(f"k = {k} > {_lib.MAX_K_WIDE} is not supported by this build")
-        if self._f8:
-            raise NotImplementedError("search_wide serves 'bf16' and 'f32' indexes; e4m3 storage is limited to search()")
-        if self._d > 1024:
-            raise NotImplementedError("search_wide serves rows of at most 1024 columns")
+        self._check_wide(k)
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         stream = _stream_handle(self.device)
         if is_dev:
@@ -247,6 +240,34 @@ class MipsIndex:
                        "mips_search_wide")
         del keep
         return D, I
+
+    def _check_wide(self, k: int) -> None:
+        if k < 0:
+            raise ValueError("k must be >= 0")
+        if k > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"k = {k} > {_lib.MAX_K_WIDE} is not supported by this build")
+        if self._f8:
+            raise NotImplementedError("search_wide serves 'bf16' and 'f32' indexes; e4m3 storage is limited to search()")
+        if self._d > 1024:
+            raise NotImplementedError("search_wide serves rows of at most 1024 columns")
+
+    def search_wide_packed(self, x, k: int, idx_offset: int = 0, force_ip: bool = False):
+        """Device-only search_wide returning the all-gather payload: CUDA int64 [nq, k, 2] = {float32 score bits,
+        index + idx_offset}, row for row what search_wide returns (padding included)."""
+        import torch
+
+        k = int(k)
+        self._check_wide(k)
+        ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        if not is_dev:
+            raise ValueError("search_wide_packed needs a CUDA tensor")
+        out = torch.empty((nq, k, 2), dtype=torch.int64, device=f"cuda:{self.device}")
+        flags = _lib.Q_DEVICE | _lib.OUT_DEVICE | _lib.OUT_PACKED | (_lib.FORCE_IP if force_ip else 0)
+        with self._mutex:
+            _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, None, out.data_ptr(), int(idx_offset), flags,
+                                                  _stream_handle(self.device)), "mips_search_wide")
+        del keep
+        return out
 
     def search_fused(self, x, k: int, normalize: bool = False, ignore=None, idx_offset: int = 0):
         """The scoring hook's search in one call on CUDA tensors (include/mips_hip.h, mips_search_fused): optional
@@ -461,6 +482,20 @@ def merge_topk_packed(gathered, nq: int, parts: int, k: int, metric: int = _lib.
     out_i = torch.empty((nq, k), dtype=torch.int64, device=gathered.device)
     _lib.check(lib.mips_merge_topk_packed(gathered.data_ptr(), nq, parts, k, metric, out_s.data_ptr(), out_i.data_ptr(),
                                           dev, _stream_handle(dev)), "mips_merge_topk_packed")
+    return out_s, out_i
+
+
+def merge_topk_sorted_packed(gathered, nq: int, parts: int, k: int, metric: int = _lib.METRIC_IP):
+    """merge_topk_packed for wide lists (k up to MAX_K_WIDE): same payload, same result, but every part must arrive in result
+    order (what search_packed and search_wide_packed emit) -- ranks come from binary searches in the other parts."""
+    import torch
+
+    lib = _lib.load()
+    dev = gathered.device.index
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=gathered.device)
+    out_i = torch.empty((nq, k), dtype=torch.int64, device=gathered.device)
+    _lib.check(lib.mips_merge_topk_sorted_packed(gathered.data_ptr(), nq, parts, k, metric, out_s.data_ptr(), out_i.data_ptr(),
+                                                 dev, _stream_handle(dev)), "mips_merge_topk_sorted_packed")
     return out_s, out_i
 
 

@@ -7,7 +7,9 @@ HBM, every rank scores ALL queries against its shard with the fused HIP kernel, 
 followed by a replicated k-way merge, identical on every rank.  No other data-path collective.
 
 The all-gather payload is one int64 tensor [nq, k, 2] per rank (float32 score bits, global row id):
-4096 x 5 x 16 B = 320 KiB at the headline config -- latency bound on xGMI.
+4096 x 5 x 16 B = 320 KiB at the headline config -- latency bound on xGMI.  The wide search (search_wide, 30 <= k <= 1024)
+takes the same route with a payload that is bandwidth-sized instead: 6.5 MB per rank at 4096 x 100, 64 MiB at 4096 x 1024, and
+the gathered buffer is `world` times that.
 """
 from __future__ import annotations
 
@@ -49,11 +51,13 @@ class ShardedMipsIndex:
     local_search(q, k, idx_offset) and merge(cand_s, cand_i, parts, k, metric) default to the HIP
     path (MipsIndex.search / mips_merge_topk).  They are injectable so that the partition + pack +
     all-gather + unpack plumbing can be exercised with the gloo backend on CPU-only machines, where
-    tests substitute the CPU oracle for the two device steps.
+    tests substitute the CPU oracle for the two device steps.  local_search_wide(q, k, idx_offset) is the
+    local step of search_wide (default MipsIndex.search_wide); when only one of the two local steps is
+    injected it stands in for the other.
     """
 
     def __init__(self, d: int, metric: int = _lib.METRIC_IP, dtype: str = "bf16", group=None, device=None,
-                 local_search=None, merge=None):
+                 local_search=None, merge=None, local_search_wide=None):
         import torch.distributed as dist
 
         self.d = int(d)
@@ -64,16 +68,17 @@ class ShardedMipsIndex:
         self.ntotal_global = 0
         self.lo = self.hi = 0
         self.local = None
-        if local_search is None:
+        if local_search is None and local_search_wide is None:
             from .index import MipsIndex
 
             self.local = MipsIndex(d, metric=metric, dtype=dtype, device=device)
-            local_search = self.local.search
+            local_search, local_search_wide = self.local.search, self.local.search_wide
         self._fast = self.local is not None and merge is None  # both device steps are the library's own
         self._device_merge = merge is None  # mips_merge_topk: candidates must be on the GPU whatever moved them
         if merge is None:
             from .index import merge_topk as merge
-        self._local_search = local_search
+        self._local_search = local_search if local_search is not None else local_search_wide
+        self._local_search_wide = local_search_wide if local_search_wide is not None else local_search
         self._merge = merge
 
     # ------------------------------------------------------------------ building
@@ -178,7 +183,7 @@ class ShardedMipsIndex:
                                   local_search=lambda *a, **k: None)  # placeholder: the local index comes from the file
         lo, hi = self.set_global_size(meta["ntotal"])
         self.local = MipsIndex.load(path, device=device, row_range=(lo, hi))
-        self._local_search = self.local.search
+        self._local_search, self._local_search_wide = self.local.search, self.local.search_wide
         self._fast = True
         self.meta = meta
         if self.metric_type == _lib.METRIC_L2 and meta.get("phi") is None:
@@ -245,10 +250,13 @@ class ShardedMipsIndex:
         The caller can enqueue the NEXT batch's scan before asking for this batch's result(): the scan of batch t + 1
         starts right behind the scan of batch t, the ~45 us tail and the latency-bound collective (tens of us against a
         ~0.6 ms shard scan at 8 GPUs) run beside it.  Falls back to the synchronous path when there is nothing to
-        overlap with (host queries, injected device steps, gloo)."""
+        overlap with (host queries, injected device steps, gloo).  k > MAX_K: the result of search_wide, already complete --
+        the wide search has no two-stream form."""
         import torch
         import torch.distributed as dist
 
+        if int(k) > _lib.MAX_K:
+            return ShardedMipsIndex._Pending(self.search_wide(q, k), None, None)
         backend = dist.get_backend(self.group) if dist.is_initialized() else None
         collective = self.world > 1 or _force_collective
         fast = (self.local is not None and self._fast and isinstance(q, torch.Tensor) and q.is_cuda
@@ -309,12 +317,47 @@ class ShardedMipsIndex:
         s, i = self._local_search(q, k, self.lo)
         return self._exchange(s, i, k, self.metric_type)
 
+    def search_wide(self, q, k: int, idx_offset: int = 0, force_ip: bool = False):
+        """search() for k up to MAX_K_WIDE = 1024 (route_search sends k > MAX_K here): every shard runs MipsIndex.search_wide,
+        then the same ONE all-gather, then the merge for sorted lists (mips_merge_topk_sorted_packed: the counting merge of
+        search() is quadratic in world * k).  bf16 and f32 shards of at most 1024 columns; idx_offset must be 0; force_ip as in
+        search().  Every query is certified or settled on its shard, so margin_stats() reports unresolved = 0.  The payload is
+        nq * k * 16 bytes per rank -- bandwidth- rather than latency-sized -- and the gathered buffer `world` times that."""
+        import torch
+        import torch.distributed as dist
+
+        if idx_offset:
+            raise ValueError("ShardedMipsIndex.search_wide returns global row numbers; idx_offset must be 0")
+        k = int(k)
+        if k > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"k = {k} > {_lib.MAX_K_WIDE} is not supported by this build")
+        if self.local is not None:
+            self.local._check_wide(k)  # e4m3 storage, more than 1024 columns: refused as MipsIndex refuses them
+        metric = _lib.METRIC_IP if force_ip else self.metric_type
+        if (self.world > 1 and self.local is not None and self._fast and isinstance(q, torch.Tensor) and q.is_cuda):
+            # device fast path, as in search(): the shard's result leaves as the payload, the merge reads it as it arrives
+            from .index import merge_topk_sorted_packed
+
+            packed = self.local.search_wide_packed(q, k, self.lo, force_ip=force_ip)
+            nq = packed.shape[0]
+            if dist.get_backend(self.group) == "gloo":
+                packed = packed.cpu()
+            gathered = torch.empty((self.world * nq, k, 2), dtype=torch.int64, device=packed.device)
+            dist.all_gather_into_tensor(gathered, packed, group=self.group)  # the ONE collective of the path
+            if not gathered.is_cuda:
+                gathered = gathered.to(q.device)
+            return merge_topk_sorted_packed(gathered, nq, self.world, k, metric)
+        s, i = self._local_search_wide(q, k, self.lo, **({"force_ip": True} if force_ip else {}))
+        return self._exchange(s, i, k, metric)
+
     def _search_force_ip(self, q, k: int):
         s, i = self.local.search(q, k, self.lo, force_ip=True)
         return self._exchange(s, i, k, _lib.METRIC_IP)
 
     def _exchange(self, s, i, k: int, metric: int):
-        """Generic form of the exchange step: pack the local top-k, ONE all-gather, unpack, merge."""
+        """Generic form of the exchange step: pack the local top-k, ONE all-gather, unpack, merge.  k > MAX_K with the
+        library's own device merge: the gathered payload goes to the merge for sorted lists as it is (the local lists must be
+        in result order, which every local search of the library and the oracle emits)."""
         import torch
         import torch.distributed as dist
 
@@ -337,8 +380,13 @@ class ShardedMipsIndex:
         dist.all_gather_into_tensor(gathered, packed, group=self.group)  # the ONE collective of the path
         if gathered.device != home:
             gathered = gathered.to(home)
-        cs, ci = unpack_gathered(gathered.view((self.world, nq) + tuple(packed.shape[1:])), self.world)
-        out_s, out_i = self._merge(cs, ci, self.world, k, metric)
+        if self._device_merge and k > _lib.MAX_K:
+            from .index import merge_topk_sorted_packed
+
+            out_s, out_i = merge_topk_sorted_packed(gathered, nq, self.world, k, metric)
+        else:
+            cs, ci = unpack_gathered(gathered.view((self.world, nq) + tuple(packed.shape[1:])), self.world)
+            out_s, out_i = self._merge(cs, ci, self.world, k, metric)
         if as_numpy:
             return out_s.cpu().numpy(), out_i.cpu().numpy()
         return out_s, out_i
