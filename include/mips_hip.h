@@ -200,6 +200,32 @@ int mips_search_split(mips_index_t* index, const void* q, int q_dtype, int64_t n
 int mips_search_wide(mips_index_t* index, const void* q, int q_dtype, int64_t nq, int k, float* out_scores,
                      int64_t* out_idx, int64_t idx_offset, int flags, void* hip_stream);
 
+/* Exact RANGE search: every stored row within a radius of each query -- faiss IndexFlat.range_search(x, radius) -> (lims, D, I);
+ * threshold retrieval ("all memories with similarity above t") and the self-join that finds duplicated rows before indexing.
+ * Membership is the FAISS rule applied to the canonical score (the value mips_search returns), both comparisons strict:
+ *   inner product   row i belongs to query j  iff  (float)dot > radii[j]
+ *   L2              row i belongs to query j  iff  (float)(|q|^2 + phi - 2 dot) < radii[j]
+ * (MIPS_FORCE_IP applies the inner-product rule on an L2 index.)
+ *   q          [nq, d] row-major, q_dtype F32 or BF16, host or device (MIPS_Q_DEVICE)
+ *   radii      HOST [nq] float32, one radius per query.  NaN: MIPS_E_INVALID; +-inf are legal (everything / nothing)
+ *   out_lims   [nq + 1] int64, out_scores [cap] float32, out_idx [cap] int64 -- all three host, or all three device
+ *              (MIPS_OUT_DEVICE)
+ * Result in CSR form: the hits of query j are out_scores / out_idx [out_lims[j], out_lims[j + 1]), out_lims[0] = 0; within a
+ * query the hits are in ASCENDING ROW ORDER (faiss leaves the order undefined; a fixed one makes two calls agree bit for bit),
+ * scores are the canonical float32 values, ids are row + idx_offset.
+ * Overflow: out_lims ALWAYS holds the true counts.  If out_lims[nq] > cap the call still returns MIPS_OK, out_scores / out_idx
+ * are unspecified and the caller repeats the call with a larger cap; cap = 0 with NULL output arrays is a legal counting call.
+ * Served: bf16 and fp32-exact indexes of at most 1024 columns, both metrics.  MIPS_E_UNSUPPORTED: e4m3 storage, rows of more
+ * than 1024 columns (the limits of mips_search_wide).  MIPS_OUT_PACKED: MIPS_E_INVALID.
+ * How: the index is walked in chunks of at most 8192 rows; the wide search's threshold scan runs with a per-query threshold that
+ * never moves -- the radius's image in the dot domain lowered by the bound on the scan's error, so the appended rows are a
+ * provable superset of the members -- and an exact filter keeps the rows whose canonical score passes the rule (DESIGN.md "Range
+ * search").  Nothing is ever uncertified: mips_index_margin_stats reports 0 / 0 / 0 afterwards, mips_index_last_kernel names the
+ * scan kernel.  Device-output calls enqueue everything on the stream and never synchronise; host-output calls synchronise once,
+ * at the end.  Scratch: the wide search's segment budget plus O(cap) staging entries and 12 bytes per (query of a slice, chunk). */
+int mips_range_search(mips_index_t* index, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
+                      float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, void* hip_stream);
+
 /* The device-resident scoring hook in one call: what retriever_generator.py:143-153 -> mips.py:421-422 does per
  * training / generation step -- `_prepare_query` (row normalisation for the normalised inner-product index,
  * mips.py:369-370), `search` with k or k + 1 hits and the `ignore_indexes` filter of mips.py:388-398 -- on DEVICE

@@ -25,11 +25,13 @@
 #include "tiny_search.hpp"
 #include "resolve_kernels.hpp"
 #include "scan_kernel_wide.hpp"
+#include "range_kernels.hpp"
 
 #include "host_state.hpp"
 #include "host_launch.hpp"
 #include "host_search.hpp"
 #include "host_wide.hpp"
+#include "host_range.hpp"
 
 extern "C" {
 
@@ -141,6 +143,10 @@ int mips_index_destroy(mips_index_t* ix) {
     ix->w_pool.release();
     ix->w_cnt.release();
     ix->w_misc.release();
+    ix->r_stage.release();
+    ix->r_blk.release();
+    ix->r_misc.release();
+    ix->r_lims.release();
     for (int e = 0; e < mips_index::kEvRing; ++e) {
         if (ix->ev0[e]) (void)hipEventDestroy(ix->ev0[e]);
         if (ix->ev1[e]) (void)hipEventDestroy(ix->ev1[e]);
@@ -559,6 +565,70 @@ int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, i
             ix->last_flagged = (int64_t)ix->nflag_host[0];
             ix->last_rescanned = ix->last_flagged;
         }
+    }
+    return MIPS_OK;
+}
+
+int mips_range_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims, float* out_scores,
+                      int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "mips_range_search: index is NULL");
+    if (nq < 0 || cap < 0) return fail(MIPS_E_INVALID, "mips_range_search: negative nq or cap");
+    if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_INVALID, "mips_range_search: MIPS_OUT_PACKED does not apply to a CSR result");
+    if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "mips_range_search: e4m3 storage is not served (bf16 and fp32-exact indexes only)");
+    if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
+        return fail(MIPS_E_UNSUPPORTED, "mips_range_search: stored rows of more than 1024 columns are not served");
+    if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "mips_range_search: q_dtype must be F32 or BF16");
+    if (!out_lims || (nq > 0 && (!q || !radii)) || (cap > 0 && (!out_scores || !out_idx))) return fail(MIPS_E_INVALID, "mips_range_search: NULL buffer");
+    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_range_search: more than 2^24 queries in one call");
+    for (int64_t j = 0; j < nq; ++j)
+        if (radii[j] != radii[j]) return fail(MIPS_E_INVALID, "mips_range_search: radii[%lld] is NaN", (long long)j);
+    DeviceGuard g(ix->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    {
+        const int prev = take_scan_error(ix, "mips_range_search");
+        if (prev) return prev;
+    }
+    ORDER_ON(ix, st);
+    if (ix->tail_pending[ix->cur_set]) { // a split-tail search still reading the staged queries of this scratch set
+        HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[ix->cur_set], 0));
+        ix->tail_pending[ix->cur_set] = false;
+    }
+    const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
+    ix->call_metric = (flags & MIPS_FORCE_IP) ? MIPS_METRIC_IP : ix->metric;
+    int64_t* d_lims = out_lims;
+    float* d_s = out_scores;
+    int64_t* d_i = out_idx;
+    if (!out_dev) {
+        int rc = ix->r_lims.ensure((size_t)(nq + 1) * sizeof(int64_t));
+        if (rc) return rc;
+        rc = ix->out_s.ensure((size_t)cap * sizeof(float));
+        if (rc) return rc;
+        rc = ix->out_i.ensure((size_t)cap * sizeof(int64_t));
+        if (rc) return rc;
+        d_lims = (int64_t*)ix->r_lims.p;
+        d_s = (float*)ix->out_s.p;
+        d_i = (int64_t*)ix->out_i.p;
+    }
+    if (nq == 0 || ix->ntotal == 0) { // no hits: every limit is 0
+        HIP_TRY(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st));
+    } else {
+        const int rc = range_search(ix, q, q_dtype, nq, radii, d_lims, d_s, d_i, cap, idx_offset, (flags & MIPS_Q_DEVICE) != 0, st);
+        if (rc) return rc;
+    }
+    // nothing is ever uncertified: the candidates are a provable superset and the filter decides on the canonical score
+    ix->last_flagged = 0;
+    ix->last_rescanned = 0;
+    ix->last_unresolved = 0;
+    ix->last_max_n = 0;
+    ix->last_fallback = false;
+    ix->first_nflag_dev = nullptr;
+    if (!out_dev) {
+        HIP_TRY(hipMemcpyAsync(out_lims, d_lims, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        if (cap > 0) {
+            HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)cap * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return MIPS_OK;
 }

@@ -51,7 +51,8 @@ def normalize_L2(x: np.ndarray) -> None:
 
 
 class IndexFlat:
-    """faiss.IndexFlat(d, metric): d, ntotal, metric_type, is_trained, verbose, nprobe, add / train / search / reset."""
+    """faiss.IndexFlat(d, metric): d, ntotal, metric_type, is_trained, verbose, nprobe, add / train / search / range_search /
+    reset."""
 
     is_trained = True
 
@@ -123,6 +124,23 @@ class IndexFlat:
         from .index import route_search
 
         return route_search(ix, q, int(k))   # k > MAX_K: the wide search (k <= MAX_K_WIDE = 1024)
+
+    def range_search(self, x, thresh):
+        """faiss Index.range_search(x, thresh) -> (lims uint64 [nq + 1], D float32, I int64): inner product, every row scoring
+        strictly above thresh; L2 (queries prepared by augment_xq, as in search), every row whose augmented squared distance
+        |q|^2 + phi - 2 q.x is strictly below it.  The hits of query j are D / I [lims[j] : lims[j + 1]], in ascending row order
+        (faiss leaves the order undefined).  NumPy in, NumPy out."""
+        ix = self._index()
+        q = np.ascontiguousarray(x, dtype=np.float32)
+        if self.metric_type == METRIC_L2:
+            if q.ndim != 2 or q.shape[1] != self.d:
+                raise ValueError(f"range_search: expected [nq, {self.d}], got {q.shape}")
+            if np.any(q[:, -1] != 0):
+                raise ValueError("L2 range_search: the queries' last (augmentation) column is not zero; this index answers "
+                                 "queries prepared by augment_xq (sotasum/mips.py:68-70)")
+            q = np.ascontiguousarray(q[:, :-1])
+        lims, D, I = ix.range_search(q, thresh)
+        return (np.asarray(lims).astype(np.uint64), np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(I, dtype=np.int64))
 
 
 class IndexFlatIP(IndexFlat):

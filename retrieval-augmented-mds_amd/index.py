@@ -251,6 +251,79 @@ class MipsIndex:
         if self._d > 1024:
             raise NotImplementedError("search_wide serves rows of at most 1024 columns")
 
+    # ------------------------------------------------------------------ range search
+    def _check_range(self) -> None:
+        if self._f8:
+            raise NotImplementedError("range_search serves 'bf16' and 'f32' indexes; e4m3 storage is limited to search()")
+        if self._d > 1024:
+            raise NotImplementedError("range_search serves rows of at most 1024 columns")
+
+    @staticmethod
+    def _radii(radius, nq: int) -> np.ndarray:
+        """A scalar or an array-like of length nq -> host float32 [nq] (mips_range_search takes the radii from the host)."""
+        r = np.asarray(radius.detach().cpu() if hasattr(radius, "detach") else radius, dtype=np.float32)
+        if r.ndim == 0:
+            r = np.full(nq, r, dtype=np.float32)
+        r = np.ascontiguousarray(r.reshape(-1))
+        if r.shape[0] != nq:
+            raise ValueError(f"range_search: expected a scalar radius or {nq} radii, got {r.shape[0]}")
+        if np.isnan(r).any():
+            raise ValueError("range_search: a radius is NaN")
+        return r
+
+    def range_search_into(self, x, radius, lims, D, I, idx_offset: int = 0, force_ip: bool = False) -> None:
+        """The non-synchronising form of range_search: the caller allocates the CUDA tensors lims (int64 [nq + 1]), D (float32
+        [cap]) and I (int64 [cap]); everything is enqueued on the current stream.  lims always receives the true counts; when
+        lims[-1] > cap the contents of D and I are unspecified and the call is to be repeated with larger tensors.  cap = 0
+        (empty D and I) is a counting call.  `radius` is host data (a scalar or nq values)."""
+        import torch
+
+        self._check_range()
+        ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        r = self._radii(radius, nq)
+        dev = torch.device("cuda", self.device)
+        for t, dt, what in ((lims, torch.int64, "lims"), (D, torch.float32, "D"), (I, torch.int64, "I")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError(f"range_search_into: {what} must be a contiguous 1-d CUDA {dt} tensor on cuda:{self.device}")
+        if lims.shape[0] != nq + 1 or D.shape[0] != I.shape[0]:
+            raise ValueError(f"range_search_into: lims must have {nq + 1} entries and D, I one length")
+        cap = int(D.shape[0])
+        flags = _lib.OUT_DEVICE | (_lib.Q_DEVICE if is_dev else 0) | (_lib.FORCE_IP if force_ip else 0)
+        with self._mutex:
+            _lib.check(self._lib.mips_range_search(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
+                                                   D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
+                                                   int(idx_offset), flags, _stream_handle(self.device)), "mips_range_search")
+        del keep
+
+    def range_search(self, x, radius, idx_offset: int = 0, force_ip: bool = False):
+        """faiss Index.range_search(x, radius) -> (lims, D, I): every stored row whose canonical score is strictly above the
+        radius (inner product; L2: whose distance |q|^2 + phi - 2 q.x is strictly below it).  `radius` is a scalar or nq
+        values.  The hits of query j are D / I [lims[j] : lims[j + 1]], in ascending row order; lims is int64 [nq + 1].
+        NumPy in -> NumPy out; torch CUDA tensor in -> torch CUDA tensors out.  The result's size is not known beforehand: a
+        first call runs with a guessed capacity, lims[-1] is READ ON THE HOST -- THIS SYNCHRONISES the stream -- and one repeat
+        with the exact size follows if the guess was too small (range_search_into is the form that never synchronises).
+        bf16 and f32 indexes of at most 1024 columns."""
+        import torch
+
+        self._check_range()
+        ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        r = self._radii(radius, nq)
+        dev = f"cuda:{self.device}"
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        cap = max(1 << 16, 256 * nq)
+        while True:
+            D = torch.empty(cap, dtype=torch.float32, device=dev)
+            I = torch.empty(cap, dtype=torch.int64, device=dev)
+            self.range_search_into(keep, r, lims, D, I, idx_offset=idx_offset, force_ip=force_ip)
+            total = int(lims[-1].item())   # the synchronisation
+            if total <= cap:
+                break
+            cap = total
+        D, I = D[:total], I[:total]
+        if is_dev:
+            return lims, D.clone() if total < cap else D, I.clone() if total < cap else I
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
     def search_wide_packed(self, x, k: int, idx_offset: int = 0, force_ip: bool = False):
         """Device-only search_wide returning the all-gather payload: CUDA int64 [nq, k, 2] = {float32 score bits,
         index + idx_offset}, row for row what search_wide returns (padding included)."""

@@ -208,6 +208,7 @@ class KnowledgeBase:
     def __init__(self, columns: dict, index: MipsIndex = None, index_name: str = "mips_embeddings"):
         self.columns = columns
         self._indexes = {index_name: _IndexHolder(index)} if index is not None else {}
+        self._index_columns = {}   # index name -> the column add_faiss_index built it from
 
     def __len__(self):
         return len(next(iter(self.columns.values()))) if self.columns else 0
@@ -225,9 +226,11 @@ class KnowledgeBase:
 
     def add_index(self, name: str, index: MipsIndex):
         self._indexes[name] = _IndexHolder(index)
+        self._index_columns.pop(name, None)
 
     def drop_index(self, name: str):
         self._indexes.pop(name, None)
+        self._index_columns.pop(name, None)
 
     def add_faiss_index(self, column: str, index_name: str = None, device: int = None, string_factory: str = None,
                         metric_type: int = None, custom_index=None, batch_size: int = 1000, train_size: int = None,
@@ -248,6 +251,7 @@ class KnowledgeBase:
         index_name = index_name if index_name is not None else column
         if custom_index is not None:
             self._indexes[index_name] = _IndexHolder(custom_index)
+            self._index_columns[index_name] = column
             return self
         metric = METRIC_L2 if metric_type is None else int(metric_type)
         x = np.asarray(self.columns[column], dtype=np.float32)
@@ -269,7 +273,45 @@ class KnowledgeBase:
         for r0 in range(0, x.shape[0], max(int(batch_size), 1 << 16)):  # HF adds in batches; rows are converted on the device
             index.add(x[r0:r0 + max(int(batch_size), 1 << 16)])
         self._indexes[index_name] = _IndexHolder(index)
+        self._index_columns[index_name] = column
         return self
+
+    def near_duplicates(self, index_name: str, threshold: float, batch_rows: int = 4096):
+        """The self-join that finds duplicated and near-duplicated rows (they are what breaks the recall of the
+        rounded storage types): range-searches the indexed column against its own index, `batch_rows` rows per call, and
+        returns every pair of rows i < j the index puts within `threshold` of each other -- inner product (cosine on normalised
+        rows): canonical score strictly ABOVE it; L2: augmented squared distance strictly BELOW it -- as (i int64, j int64,
+        score float32) sorted by (i, j).  Fixed-k search cannot answer this: a cluster of 65 copies overflows any k chosen for
+        the other rows.  An L2 index takes the stripped (un-augmented) rows, as add_faiss_index stored them.  Indexes that were
+        not built by add_faiss_index are joined on their stored rows (rows_raw)."""
+        index = self.get_index(index_name).faiss_index
+        column = self._index_columns.get(index_name)
+        if column is not None:
+            x = np.asarray(self.columns[column], dtype=np.float32)
+            if index.metric_type == METRIC_L2 and x.shape[1] == index.d + 1:
+                x = x[:, :-1]
+            n = x.shape[0]
+            rows = lambda r0, r1: np.ascontiguousarray(x[r0:r1])
+        elif hasattr(index, "rows_raw"):
+            n = index.ntotal
+            rows = lambda r0, r1: index.rows_raw(r0, r1 - r0)
+        else:
+            raise ValueError(f"near_duplicates: index {index_name!r} was not built by add_faiss_index and cannot return its rows")
+        step = max(1, int(batch_rows))
+        out_i, out_j, out_s = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros(0, np.float32)]
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            lims, D, I = index.range_search(rows(r0, r1), float(threshold))
+            lims = np.asarray(lims).astype(np.int64)
+            qi = np.repeat(np.arange(r0, r1, dtype=np.int64), np.diff(lims))
+            I = np.asarray(I, dtype=np.int64)
+            keep = qi < I   # each unordered pair once, no row with itself
+            out_i.append(qi[keep])
+            out_j.append(I[keep])
+            out_s.append(np.asarray(D, dtype=np.float32)[keep])
+        i, j, s = np.concatenate(out_i), np.concatenate(out_j), np.concatenate(out_s)
+        order = np.lexsort((j, i))
+        return i[order], j[order], s[order]
 
     def get_nearest_examples_batch(self, index_name: str, queries, k: int = 10):
         """HF Dataset.get_nearest_examples_batch as used at retriever_lightning.py:317-321: returns (scores
