@@ -59,6 +59,7 @@ extern "C" {
 #define MIPS_FORCE_IP 8   /* rank by inner product for this call even on an L2 index (Mips.np_search, mips.py:527-529) */
 #define MIPS_OUT_PACKED 4 /* with MIPS_OUT_DEVICE: out_idx receives [nq, k, 2] int64 = {float32 score bits
                              (zero-extended), index}, the all-gather payload; out_scores is ignored */
+#define MIPS_SEL_DEVICE 16 /* mips_search_wide_sel / mips_range_search_sel: sel_bits is device memory */
 
 /* synthetic data kinds (same functions as oracle/synth.py) */
 #define MIPS_SYNTH_LATTICE 0
@@ -225,6 +226,28 @@ int mips_search_wide(mips_index_t* index, const void* q, int q_dtype, int64_t nq
  * at the end.  Scratch: the wide search's segment budget plus O(cap) staging entries and 12 bytes per (query of a slice, chunk). */
 int mips_range_search(mips_index_t* index, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
                       float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, void* hip_stream);
+
+/* FILTERED wide top-k and range search: "search only these rows" -- the faiss IDSelector of IndexFlat.search / range_search
+ * (SearchParameters(sel=...)).  The selector is a bitmap in the faiss IDSelectorBitmap layout, one for all queries of the call:
+ *   sel_bits   uint8 [(sel_nbits + 7) / 8], host or device (MIPS_SEL_DEVICE); bit b is sel_bits[b >> 3] >> (b & 7) & 1
+ *   sel_bit0   bit sel_bit0 + i decides LOCAL row i (a row shard passes the global bitmap and its first global row, which need
+ *              not be a multiple of 8).  sel_bit0 < 0 or sel_bit0 + ntotal > sel_nbits: MIPS_E_INVALID
+ * The result is what the unfiltered call returns on an index from which the unselected rows were deleted while the remaining rows
+ * keep their numbers and the index keeps its phi and maximal norm: same canonical score (L2 distances use the index's phi), same
+ * order and tie rule, strict range rule, ascending rows in a range result, -1 / -+inf padding when fewer than k rows are selected;
+ * idx_offset, MIPS_FORCE_IP and (wide only) MIPS_OUT_PACKED as in the unfiltered calls, and so are the served storages and limits
+ * (k <= MIPS_MAX_K is legal).  sel_bits == NULL IS the unfiltered call: same code path, same kernels, same bits.
+ * How: one staging kernel per call turns the bitmap into per-tile words and counts the selected rows on the device; the threshold
+ * scan runs as its masked instance (mips_index_last_kernel: "mips::masked_scan_kernel"), which skips 128-row tiles without a
+ * selected row and never appends an unselected one; the certificate of the wide search counts the selected rows where it counted
+ * ntotal, and the exact settlement tests the row's bit before it appends (DESIGN.md "Filtered search").  Every filtered wide
+ * search is certified or settled in the call (unresolved = 0); a filtered range search reports 0 / 0 / 0.  Device-output calls
+ * never synchronise: a host bitmap travels by the stream's asynchronous copy (it must stay valid until the call returns). */
+int mips_search_wide_sel(mips_index_t* index, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                         int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream);
+int mips_range_search_sel(mips_index_t* index, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
+                          float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags,
+                          const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream);
 
 /* The device-resident scoring hook in one call: what retriever_generator.py:143-153 -> mips.py:421-422 does per
  * training / generation step -- `_prepare_query` (row normalisation for the normalised inner-product index,

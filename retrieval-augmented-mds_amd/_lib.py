@@ -23,7 +23,7 @@ ABI_VERSION = 1
 # constants of include/mips_hip.h
 DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3, DTYPE_FP8_E4M3_DOCS = 0, 1, 2, 3
 METRIC_IP, METRIC_L2 = 0, 1
-Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP = 1, 2, 4, 8
+Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP, SEL_DEVICE = 1, 2, 4, 8, 16
 SYNTH_LATTICE, SYNTH_GAUSS, SYNTH_LATTICE_FP8 = 0, 1, 2
 SEED_DOCS, SEED_QUERIES = 0xD0C5, 0x0E21  # fixed seeds of the synthetic workloads
 MAX_K = 29
@@ -108,6 +108,8 @@ def _bind(lib):
         "mips_search": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp]),
         "mips_search_wide": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp]),
         "mips_range_search": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, i64, i32, vp]),
+        "mips_search_wide_sel": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, i64, i64, vp]),
+        "mips_range_search_sel": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, i64, i32, vp, i64, i64, vp]),
         "mips_search_split": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, vp]),
         "mips_search_fused": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp, i64, vp]),
         "mips_merge_topk": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, i32, vp]),
@@ -141,6 +143,7 @@ EXPORTS = (
     "mips_merge_topk_packed", "mips_filter_ignore", "mips_cosine_rescore", "mips_cosine_rescore_bias", "mips_l2_normalize", "mips_rows_max_sumsq", "mips_index_set_param", "mips_scan_timing",
     "mips_index_check_error", "mips_index_last_kernel", "mips_cosine_rescore_backward", "mips_index_margin_stats", "mips_search_fused", "mips_search_split",
     "mips_rows_max_sumsq_device", "mips_search_wide", "mips_merge_topk_sorted_packed", "mips_range_search",
+    "mips_search_wide_sel", "mips_range_search_sel",
 )
 
 

@@ -9,7 +9,8 @@ static_assert(kWideSlice == 4 * mips::RANGE_LIMS_THREADS, "range_lims_kernel tak
 
 // d_lims [nq + 1], d_s / d_i [cap] are DEVICE buffers; radii is the caller's HOST array.  nq > 0 and ntotal > 0.
 int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* d_lims, float* d_s, int64_t* d_i, int64_t cap,
-                 int64_t idx_offset, bool q_dev, hipStream_t st) {
+                 int64_t idx_offset, bool q_dev, Selector sel, hipStream_t st) {
+    const bool masked = sel.bits != nullptr; // a filtered search: only the scan changes, the filter sees appended rows alone
     const bool f32x = ix->plane > 0;
     const bool l2 = ix->call_metric == MIPS_METRIC_L2;
     const int sld = f32x ? ix->hp : ix->ld;    // row pitch of the scanned bf16 rows
@@ -67,7 +68,13 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
     const size_t qesz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
     const double err_c = (double)ix->d * 1.1920928955078125e-07 * (f32x ? 1.01 : 1.0);
     const int scan_lds = mips::SCAN_LDS_BYTES;
-    HIP_TRY(hipFuncSetAttribute((const void*)mips::wide_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+    if (masked) {
+        HIP_TRY(hipFuncSetAttribute((const void*)mips::masked_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+        rc = stage_selector(ix, sel, st);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(hipFuncSetAttribute((const void*)mips::wide_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+    }
 
     for (int64_t s0 = 0; s0 < nq; s0 += slice) {
         const int64_t ns = std::min(slice, nq - s0);
@@ -136,6 +143,7 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
         sa.segcap = segcap;
         sa.cnt = (int*)ix->w_cnt.p;
         sa.tiles_per_split = tps;
+        sa.sel = sel.words;
         mips::RangeFilterArgs fa;
         fa.seg = sa.seg;
         fa.nseg = nseg;
@@ -160,7 +168,8 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
             sa.tile_end = (int)std::min<int64_t>(ntiles, sa.tile0 + chunk_tiles);
             fa.row0 = sa.tile0 * mips::TM;
             fa.chunk = chunk;
-            mips::wide_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            if (masked) mips::masked_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            else mips::wide_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
             if (f32x) {
                 if (l2) mips::range_filter_kernel<mips::ElemF32, true><<<(int)ns, mips::RANGE_THREADS, 0, st>>>(fa);
                 else mips::range_filter_kernel<mips::ElemF32, false><<<(int)ns, mips::RANGE_THREADS, 0, st>>>(fa);
@@ -198,7 +207,7 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
         }
         HIP_TRY(hipGetLastError());
     }
-    set_kernel_name(ix, "mips::wide_scan_kernel");
+    set_kernel_name(ix, masked ? "mips::masked_scan_kernel" : "mips::wide_scan_kernel");
     return MIPS_OK;
 }
 

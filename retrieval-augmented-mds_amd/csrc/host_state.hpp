@@ -141,6 +141,9 @@ struct mips_index {
     // range search (mips_range_search, host_range.hpp; it shares w_seg / w_cnt): staging of the members in O(cap), the
     // (offset, count) of every (query, chunk) block, per-query thresholds / totals / radii, and the CSR arrays of a host-output call
     Buffer r_stage, r_blk, r_misc, r_lims;
+    // filtered searches (mips_search_wide_sel / mips_range_search_sel): the device copy of a host bitmap, and the staged selector
+    // ([0] the number of selected rows, from byte 16 on four 32-bit words per 128-row tile; select_kernels.hpp)
+    Buffer sel_raw, sel_words;
     int opt_resolve = 1; // flagged queries: 1 = exact brute-force resolution (resolve_kernels.hpp; 2 = its plain form, no MFMA pre-filter), 0 = re-scan with the widest lists
     int resolve_budget = 0; // "resolve_budget" > 0: flagged queries a search resolves at most (0 = RESOLVE_MAX); a search that flags
                             // more keeps its first results (counted unresolved) -- or, if its first scan was an optimistic one,

@@ -27,9 +27,49 @@ struct WideScratch {
     unsigned* words; // [0] flagged queries of the call, [1] always 0 (unresolved)
 };
 
+// A caller's row selector (bits == nullptr: none) and, once staged, what the kernels read.
+struct Selector {
+    const uint8_t* bits = nullptr;
+    int64_t nbits = 0, bit0 = 0;
+    bool dev = false;                          // bits is device memory (MIPS_SEL_DEVICE)
+    const unsigned* words = nullptr;           // staged: four words per 128-row tile
+    const unsigned long long* nsel = nullptr;  // staged: number of selected rows
+};
+
+// Runs once per call, before the first slice: the bitmap (a host one is copied with the stream's async copy) becomes the
+// shifted, cleared and padded words of select_kernels.hpp, and their popcount.  Nothing is read back.
+int stage_selector(mips_index* ix, Selector& sel, hipStream_t st) {
+    const int64_t ntiles = (ix->ntotal + mips::TM - 1) / mips::TM;
+    const int64_t nwords = ntiles * (mips::TM / 32);
+    int rc = ix->sel_words.ensure(16 + (size_t)nwords * sizeof(unsigned));
+    if (rc) return rc;
+    const uint8_t* src = sel.bits;
+    int64_t bit0 = sel.bit0;
+    int64_t nbytes = (sel.nbits + 7) >> 3;
+    if (!sel.dev) { // only the bytes that hold bits bit0 .. bit0 + ntotal - 1 travel
+        const int64_t b0 = sel.bit0 >> 3, b1 = (sel.bit0 + ix->ntotal + 7) >> 3;
+        rc = ix->sel_raw.ensure((size_t)(b1 - b0));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ix->sel_raw.p, sel.bits + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, st));
+        src = (const uint8_t*)ix->sel_raw.p;
+        bit0 = sel.bit0 & 7;
+        nbytes = b1 - b0;
+    }
+    unsigned long long* nsel = (unsigned long long*)ix->sel_words.p;
+    unsigned* words = (unsigned*)((unsigned char*)ix->sel_words.p + 16);
+    HIP_TRY(hipMemsetAsync(nsel, 0, 16, st));
+    mips::selector_stage_kernel<<<grid_for(nwords, mips::SEL_THREADS), mips::SEL_THREADS, 0, st>>>(src, nbytes, bit0, ix->ntotal, words, nwords, nsel);
+    HIP_TRY(hipGetLastError());
+    sel.words = words;
+    sel.nsel = nsel;
+    return MIPS_OK;
+}
+
 // packed: d_i is the MIPS_OUT_PACKED payload [nq][k][2] and d_s is not written (it may be NULL)
+// sel.bits != nullptr: a filtered search (masked scan, certificate on the selected count, masked settlement)
 int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool q_dev,
-                hipStream_t st) {
+                Selector sel, hipStream_t st) {
+    const bool masked = sel.bits != nullptr;
     const bool f32x = ix->plane > 0;
     const bool l2 = ix->call_metric == MIPS_METRIC_L2;
     const int sld = f32x ? ix->hp : ix->ld;    // row pitch of the scanned bf16 rows
@@ -99,7 +139,13 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
     const size_t qesz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
     const double err_c = (double)ix->d * 1.1920928955078125e-07 * (f32x ? 1.01 : 1.0);
     const int scan_lds = mips::SCAN_LDS_BYTES;
-    HIP_TRY(hipFuncSetAttribute((const void*)mips::wide_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+    if (masked) {
+        HIP_TRY(hipFuncSetAttribute((const void*)mips::masked_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+        rc = stage_selector(ix, sel, st);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(hipFuncSetAttribute((const void*)mips::wide_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+    }
 
     for (int64_t s0 = 0; s0 < nq; s0 += slice) {
         const int64_t ns = std::min(slice, nq - s0);
@@ -149,6 +195,7 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         sa.seg = (mips::wkey_t*)ix->w_seg.p;
         sa.segcap = segcap;
         sa.cnt = w.cnt;
+        sa.sel = sel.words;
         mips::WideSelArgs se;
         se.seg = sa.seg;
         se.nseg = nseg;
@@ -169,7 +216,8 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
             sa.tile0 = (int)tile;
             sa.tile_end = (int)std::min<int64_t>(ntiles, tile + (int64_t)tps * nsplit);
             sa.tiles_per_split = tps;
-            mips::wide_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            if (masked) mips::masked_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            else mips::wide_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
             mips::wide_select_kernel<<<(int)ns, mips::WIDE_THREADS, 0, st>>>(se);
             HIP_TRY(hipGetLastError());
             tile = sa.tile_end;
@@ -199,7 +247,16 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         ra.dres2 = f32x ? ix->dres2_dev : nullptr;
         ra.qerr2 = f32x ? (const double*)ix->qerr2.p : nullptr;
         ra.err_c = err_c;
-        if (f32x) {
+        ra.nsel = sel.nsel;
+        if (masked) {
+            if (f32x) {
+                if (l2) mips::wide_rescore_kernel<mips::ElemF32, true, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+                else mips::wide_rescore_kernel<mips::ElemF32, false, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+            } else {
+                if (l2) mips::wide_rescore_kernel<mips::ElemBF16, true, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+                else mips::wide_rescore_kernel<mips::ElemBF16, false, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+            }
+        } else if (f32x) {
             if (l2) mips::wide_rescore_kernel<mips::ElemF32, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
             else mips::wide_rescore_kernel<mips::ElemF32, false><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
         } else {
@@ -234,6 +291,7 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         xa.out_s = out_s;
         xa.out_i = out_i;
         xa.out_packed = out_packed;
+        xa.sel = sel.words;
         mips::WideSelArgs xe = se;
         xe.nseg = 1;
         xe.segcap = (int)xrows;
@@ -255,7 +313,9 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
                 xa.r0 = r0;
                 xa.r1 = std::min(ix->ntotal, r0 + xrows);
                 const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(512, (xa.r1 - xa.r0 + 511) / 512));
-                if (f32x) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemF32, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemF32, false>, grid);
+                if (masked && f32x) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemF32, true, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemF32, false, true>, grid);
+                else if (masked) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemBF16, true, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemBF16, false, true>, grid);
+                else if (f32x) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemF32, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemF32, false>, grid);
                 else rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemBF16, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemBF16, false>, grid);
                 if (rc) return rc;
                 mips::wide_select_kernel<<<xa.nslots, mips::WIDE_THREADS, 0, st>>>(xe);
@@ -265,7 +325,7 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
             HIP_TRY(hipGetLastError());
         }
     }
-    set_kernel_name(ix, "mips::wide_scan_kernel");
+    set_kernel_name(ix, masked ? "mips::masked_scan_kernel" : "mips::wide_scan_kernel");
     // statistics: flagged = settled exactly; nothing is ever left unresolved
     ix->last_flagged = -1; // (on the device: mips_index_margin_stats fetches the two words when asked)
     ix->last_rescanned = 0;

@@ -26,6 +26,7 @@
 #include "resolve_kernels.hpp"
 #include "scan_kernel_wide.hpp"
 #include "range_kernels.hpp"
+#include "select_kernels.hpp"
 
 #include "host_state.hpp"
 #include "host_launch.hpp"
@@ -147,6 +148,8 @@ int mips_index_destroy(mips_index_t* ix) {
     ix->r_blk.release();
     ix->r_misc.release();
     ix->r_lims.release();
+    ix->sel_raw.release();
+    ix->sel_words.release();
     for (int e = 0; e < mips_index::kEvRing; ++e) {
         if (ix->ev0[e]) (void)hipEventDestroy(ix->ev0[e]);
         if (ix->ev1[e]) (void)hipEventDestroy(ix->ev1[e]);
@@ -506,24 +509,28 @@ static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq,
     return MIPS_OK;
 }
 
-int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
-                     int64_t idx_offset, int flags, void* hip_stream) {
-    if (!ix) return fail(MIPS_E_INVALID, "mips_search_wide: index is NULL");
-    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_search_wide: negative nq or k");
-    if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: k = %d exceeds MIPS_MAX_K_WIDE = %d", k, MIPS_MAX_K_WIDE);
-    if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: e4m3 storage is not served (bf16 and fp32-exact indexes only)");
+// sel_bits == NULL: the unfiltered search (sel_nbits and sel_bit0 are not looked at)
+static int search_wide_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                            int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
+    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "%s: negative nq or k", who);
+    if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "%s: k = %d exceeds MIPS_MAX_K_WIDE = %d", who, k, MIPS_MAX_K_WIDE);
+    if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "%s: e4m3 storage is not served (bf16 and fp32-exact indexes only)", who);
     if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
-        return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: stored rows of more than 1024 columns are not served");
-    if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "mips_search_wide: q_dtype must be F32 or BF16");
+        return fail(MIPS_E_UNSUPPORTED, "%s: stored rows of more than 1024 columns are not served", who);
+    if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "%s: q_dtype must be F32 or BF16", who);
+    if (sel_bits && (sel_bit0 < 0 || sel_nbits < 0 || sel_bit0 > sel_nbits || ix->ntotal > sel_nbits - sel_bit0))
+        return fail(MIPS_E_INVALID, "%s: the selector's %lld bits from bit %lld on do not cover the index's %lld rows", who, (long long)sel_nbits,
+                    (long long)sel_bit0, (long long)ix->ntotal);
     if (nq == 0 || k == 0) return MIPS_OK;
     const bool packed = (flags & MIPS_OUT_PACKED) != 0;
-    if (packed && !(flags & MIPS_OUT_DEVICE)) return fail(MIPS_E_INVALID, "mips_search_wide: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE");
-    if (!q || !out_idx || (!out_scores && !packed)) return fail(MIPS_E_INVALID, "mips_search_wide: NULL buffer");
-    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_search_wide: more than 2^24 queries in one call");
+    if (packed && !(flags & MIPS_OUT_DEVICE)) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE", who);
+    if (!q || !out_idx || (!out_scores && !packed)) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
+    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "%s: more than 2^24 queries in one call", who);
     DeviceGuard g(ix->device);
     hipStream_t st = (hipStream_t)hip_stream;
     {
-        const int prev = take_scan_error(ix, "mips_search_wide");
+        const int prev = take_scan_error(ix, who);
         if (prev) return prev;
     }
     ORDER_ON(ix, st);
@@ -552,7 +559,12 @@ int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, i
         ix->last_unresolved = 0;
         ix->first_nflag_dev = nullptr;
     } else {
-        const int rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, st);
+        Selector sel;
+        sel.bits = sel_bits;
+        sel.nbits = sel_nbits;
+        sel.bit0 = sel_bit0;
+        sel.dev = (flags & MIPS_SEL_DEVICE) != 0;
+        const int rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, st);
         if (rc) return rc;
     }
     if (!out_dev) {
@@ -569,23 +581,38 @@ int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, i
     return MIPS_OK;
 }
 
-int mips_range_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims, float* out_scores,
-                      int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, void* hip_stream) {
-    if (!ix) return fail(MIPS_E_INVALID, "mips_range_search: index is NULL");
-    if (nq < 0 || cap < 0) return fail(MIPS_E_INVALID, "mips_range_search: negative nq or cap");
-    if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_INVALID, "mips_range_search: MIPS_OUT_PACKED does not apply to a CSR result");
-    if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "mips_range_search: e4m3 storage is not served (bf16 and fp32-exact indexes only)");
+int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                     int64_t idx_offset, int flags, void* hip_stream) {
+    return search_wide_impl("mips_search_wide", ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, nullptr, 0, 0, hip_stream);
+}
+
+int mips_search_wide_sel(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                         int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
+    return search_wide_impl("mips_search_wide_sel", ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, sel_bits, sel_nbits, sel_bit0,
+                            hip_stream);
+}
+
+static int range_search_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
+                             float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, const uint8_t* sel_bits,
+                             int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
+    if (nq < 0 || cap < 0) return fail(MIPS_E_INVALID, "%s: negative nq or cap", who);
+    if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED does not apply to a CSR result", who);
+    if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "%s: e4m3 storage is not served (bf16 and fp32-exact indexes only)", who);
     if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
-        return fail(MIPS_E_UNSUPPORTED, "mips_range_search: stored rows of more than 1024 columns are not served");
-    if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "mips_range_search: q_dtype must be F32 or BF16");
-    if (!out_lims || (nq > 0 && (!q || !radii)) || (cap > 0 && (!out_scores || !out_idx))) return fail(MIPS_E_INVALID, "mips_range_search: NULL buffer");
-    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_range_search: more than 2^24 queries in one call");
+        return fail(MIPS_E_UNSUPPORTED, "%s: stored rows of more than 1024 columns are not served", who);
+    if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "%s: q_dtype must be F32 or BF16", who);
+    if (!out_lims || (nq > 0 && (!q || !radii)) || (cap > 0 && (!out_scores || !out_idx))) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
+    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "%s: more than 2^24 queries in one call", who);
+    if (sel_bits && (sel_bit0 < 0 || sel_nbits < 0 || sel_bit0 > sel_nbits || ix->ntotal > sel_nbits - sel_bit0))
+        return fail(MIPS_E_INVALID, "%s: the selector's %lld bits from bit %lld on do not cover the index's %lld rows", who, (long long)sel_nbits,
+                    (long long)sel_bit0, (long long)ix->ntotal);
     for (int64_t j = 0; j < nq; ++j)
-        if (radii[j] != radii[j]) return fail(MIPS_E_INVALID, "mips_range_search: radii[%lld] is NaN", (long long)j);
+        if (radii[j] != radii[j]) return fail(MIPS_E_INVALID, "%s: radii[%lld] is NaN", who, (long long)j);
     DeviceGuard g(ix->device);
     hipStream_t st = (hipStream_t)hip_stream;
     {
-        const int prev = take_scan_error(ix, "mips_range_search");
+        const int prev = take_scan_error(ix, who);
         if (prev) return prev;
     }
     ORDER_ON(ix, st);
@@ -612,7 +639,12 @@ int mips_range_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, 
     if (nq == 0 || ix->ntotal == 0) { // no hits: every limit is 0
         HIP_TRY(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st));
     } else {
-        const int rc = range_search(ix, q, q_dtype, nq, radii, d_lims, d_s, d_i, cap, idx_offset, (flags & MIPS_Q_DEVICE) != 0, st);
+        Selector sel;
+        sel.bits = sel_bits;
+        sel.nbits = sel_nbits;
+        sel.bit0 = sel_bit0;
+        sel.dev = (flags & MIPS_SEL_DEVICE) != 0;
+        const int rc = range_search(ix, q, q_dtype, nq, radii, d_lims, d_s, d_i, cap, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, st);
         if (rc) return rc;
     }
     // nothing is ever uncertified: the candidates are a provable superset and the filter decides on the canonical score
@@ -631,6 +663,19 @@ int mips_range_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, 
         HIP_TRY(hipStreamSynchronize(st));
     }
     return MIPS_OK;
+}
+
+int mips_range_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims, float* out_scores,
+                      int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, void* hip_stream) {
+    return range_search_impl("mips_range_search", ix, q, q_dtype, nq, radii, out_lims, out_scores, out_idx, cap, idx_offset, flags, nullptr, 0, 0,
+                             hip_stream);
+}
+
+int mips_range_search_sel(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims, float* out_scores,
+                          int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits,
+                          int64_t sel_bit0, void* hip_stream) {
+    return range_search_impl("mips_range_search_sel", ix, q, q_dtype, nq, radii, out_lims, out_scores, out_idx, cap, idx_offset, flags, sel_bits,
+                             sel_nbits, sel_bit0, hip_stream);
 }
 
 int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64_t nq, int k, int normalize, const int64_t* ignore_device,

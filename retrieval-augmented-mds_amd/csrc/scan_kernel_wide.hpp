@@ -62,9 +62,13 @@ struct WideScanArgs {
     wkey_t* seg;          // [nqt * TN][2 nsplit][segcap]
     int segcap;           // >= 64 * tiles_per_split
     int* cnt;             // [nqt * TN][2 nsplit]
+    const unsigned* sel;  // masked_scan_kernel: staged selector, 4 words per tile (16-byte aligned); wide_scan_kernel: unused
 };
 
-__global__ __launch_bounds__(SCAN_THREADS, 2) void wide_scan_kernel(WideScanArgs p) {
+// SEL: the masked instance (masked_scan_kernel below).  p.sel holds four 32-bit words per tile (select_kernels.hpp): a tile whose
+// words are all zero is never loaded, and a row whose bit is clear never passes the threshold test.
+template <bool SEL>
+__device__ __forceinline__ void wide_scan_body(const WideScanArgs& p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x;
@@ -136,9 +140,33 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void wide_scan_kernel(WideScanArgs
         }
     };
 
+    // first tile at or after t that holds a selected row, or t1 (the words are wave-uniform: every wave walks the same tiles)
+    auto next_tile = [&](int t) {
+        if constexpr (SEL) {
+            const u32x4* sel4 = reinterpret_cast<const u32x4*>(p.sel);
+            while (t < t1) {
+                const u32x4 w = sel4[t];
+                if (__builtin_amdgcn_readfirstlane((int)(w[0] | w[1] | w[2] | w[3])) != 0) break;
+                ++t;
+            }
+        }
+        return t;
+    };
+
     auto epilogue = [&](int tile) {
         const int base = tile * TM + 4 * h;
-        if ((int64_t)(tile + 1) * TM > p.ntotal) { // ragged last tile: rows past ntotal never pass
+        if constexpr (SEL) { // rows past ntotal are clear bits of the staged words: no test of the ragged tile
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const unsigned wm = (unsigned)__builtin_amdgcn_readfirstlane((int)p.sel[4 * tile + m]);
+                if (wm != 0xffffffffu) {
+                    const unsigned ws = wm >> (4 * h);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        if (((ws >> ((r & 3) + 8 * (r >> 2))) & 1u) == 0u) acc[m][r] = -INFINITY;
+                }
+            }
+        } else if ((int64_t)(tile + 1) * TM > p.ntotal) { // ragged last tile: rows past ntotal never pass
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -163,6 +191,35 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void wide_scan_kernel(WideScanArgs
         }
     };
 
+    if constexpr (SEL) {
+        // the same flattened (tile, k-step) pipeline over the NON-EMPTY tiles of the split: the prefetch of the step after a
+        // tile's last k-step addresses the next non-empty tile, and a split without one stores a zero counter and leaves
+        int tile = next_tile(t0), ks = 0, buf = 0;
+        if (tile < t1) gload(tile, 0);
+        while (tile < t1) {
+            swrite(buf);
+            __syncthreads();
+            int ntile = tile, nks = ks + 1;
+            if (nks == p.ksteps) {
+                nks = 0;
+                ntile = next_tile(tile + 1);
+            }
+            if (ntile < t1) gload(ntile, nks);
+            if (ks == 0) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
+            }
+            compute(buf);
+            if (ks == p.ksteps - 1) epilogue(tile);
+            tile = ntile;
+            ks = nks;
+            buf ^= 1;
+        }
+        p.cnt[segno] = cur;
+        return;
+    }
     const int total = nt * p.ksteps;
     if (total > 0) gload(t0, 0);
     int tile = t0, ks = 0;
@@ -189,6 +246,10 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void wide_scan_kernel(WideScanArgs
     }
     p.cnt[segno] = cur;
 }
+
+__global__ __launch_bounds__(SCAN_THREADS, 2) void wide_scan_kernel(WideScanArgs p) { wide_scan_body<false>(p); }
+// the instance of the filtered searches (its name stays outside the census of scan instances, tests/scan_recipes.py)
+__global__ __launch_bounds__(SCAN_THREADS, 2) void masked_scan_kernel(WideScanArgs p) { wide_scan_body<true>(p); }
 
 // ------------------------------------------------------------------------------------------------------------- select
 // descending bitonic sort of buf[0 .. n) in LDS by the whole workgroup (n <= WIDE_BUF; pads with 0 = "no entry")
@@ -336,9 +397,12 @@ struct WideRescoreArgs {
     const double* dres2; // fp32-exact index (with qerr2), else nullptr
     const double* qerr2;
     double err_c;
+    const unsigned long long* nsel; // SEL: number of selected rows (select_kernels.hpp), a device word
 };
 
-template <typename EL, bool L2>
+// SEL: a filtered search.  The rows that can be results are the nsel selected ones, so the two uses of ntotal in the certificate
+// read that count instead.
+template <typename EL, bool L2, bool SEL = false>
 __global__ __launch_bounds__(WIDE_THREADS) void wide_rescore_kernel(WideRescoreArgs a) {
     __shared__ double yd[1024];
     __shared__ double dd[WIDE_POOL];
@@ -402,11 +466,12 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rescore_kernel(WideRescoreA
         // canonical dot <= ub = B + e; the canonical key is a monotone function of the dot, so its key is no better than
         // key(ub).  Only if that is STRICTLY worse than the k-th result's key can no such row enter the top k (an equal float32
         // key could still win on the row number).
-        const int64_t need = a.ntotal < (int64_t)a.kp ? a.ntotal : (int64_t)a.kp;
+        const int64_t nrows = SEL ? (int64_t)*a.nsel : a.ntotal;
+        const int64_t need = nrows < (int64_t)a.kp ? nrows : (int64_t)a.kp;
         bool fl = false;
         if ((int64_t)n < need) {
             fl = true;
-        } else if (a.ntotal > (int64_t)n) {
+        } else if (nrows > (int64_t)n) {
             const double B = (double)thr_decode(minhi_s);
             const double qn = sqrt(qq), xm = sqrt(*a.xmax2);
             double e = a.err_c * qn * xm;
@@ -451,6 +516,7 @@ struct WideExactArgs {
     float* out_s;
     int64_t* out_i;
     int64_t* out_packed;
+    const unsigned* sel; // SEL: staged selector words (bit r & 31 of word r >> 5 = local row r), zero past ntotal
 };
 
 // start of a round: empty pools; a row must reach the k-th result of the first pass to matter
@@ -463,7 +529,9 @@ __global__ void wide_exact_init_kernel(WideExactArgs a) {
     a.cnt[slot] = 0;
 }
 
-template <typename EL, bool L2>
+// SEL: a filtered search.  An unselected row is never appended (the settlement must not bring back what the scan left out), and a
+// wave's 64 rows are not scored at all when none of them is selected.
+template <typename EL, bool L2, bool SEL = false>
 __global__ __launch_bounds__(64 * RESOLVE_WAVES) void wide_exact_kernel(WideExactArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int n = *a.n_dev;
@@ -498,9 +566,14 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void wide_exact_kernel(WideExac
         }
         for (int64_t r0 = a.r0 + ((int64_t)blockIdx.x * RESOLVE_WAVES + wave) * 64; r0 < a.r1; r0 += (int64_t)gridDim.x * 64 * RESOLVE_WAVES) {
             const int64_t row = r0 + lane;
+            bool on = true;
+            if constexpr (SEL) {
+                on = row < a.r1 && ((a.sel[row >> 5] >> (int)(row & 31)) & 1u) != 0u;
+                if (__ballot(on) == 0ull) continue;
+            }
             double acc[RESOLVE_QB];
             exact_dots<EL>(rows, a.ld, a.ntotal, r0, lane, tile, yd, acc);
-            if (row < a.r1) {
+            if (row < a.r1 && on) {
 #pragma unroll
                 for (int j = 0; j < RESOLVE_QB; ++j) {
                     const float outv = L2 ? (float)(qn[j] + a.phi - 2.0 * acc[j]) : (float)acc[j];

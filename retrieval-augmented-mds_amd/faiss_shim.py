@@ -50,6 +50,97 @@ def normalize_L2(x: np.ndarray) -> None:
     x *= scale[:, None]
 
 
+# ---- faiss.IDSelector*: "search only these rows".  Each class answers bitmap(ntotal) -> uint8 [(ntotal + 7) // 8] in the
+# IDSelectorBitmap layout (row i is selected iff bitmap[i >> 3] >> (i & 7) & 1), bits at and past ntotal clear; ids the index does
+# not hold select nothing, as in faiss.
+class IDSelector:
+    def mask(self, ntotal: int) -> np.ndarray:   # bool [ntotal]
+        raise NotImplementedError
+
+    def bitmap(self, ntotal: int) -> np.ndarray:
+        return np.packbits(self.mask(int(ntotal)), bitorder="little")
+
+    def is_member(self, i: int) -> bool:
+        return bool(self.mask(int(i) + 1)[int(i)]) if i >= 0 else False
+
+
+class IDSelectorRange(IDSelector):
+    """Rows imin <= i < imax."""
+
+    def __init__(self, imin: int, imax: int, assume_sorted: bool = False):
+        self.imin, self.imax = int(imin), int(imax)
+
+    def mask(self, ntotal: int) -> np.ndarray:
+        r = np.arange(ntotal)
+        return (r >= self.imin) & (r < self.imax)
+
+
+class IDSelectorBatch(IDSelector):
+    """The listed rows (faiss: a hash set; IDSelectorArray: the plain list -- the same selection)."""
+
+    def __init__(self, ids, *more):
+        if more:   # the SWIG spelling IDSelectorBatch(n, ids)
+            ids = np.asarray(more[0]).reshape(-1)[: int(ids)]
+        self.ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+
+    def mask(self, ntotal: int) -> np.ndarray:
+        m = np.zeros(ntotal, dtype=np.bool_)
+        m[self.ids[(self.ids >= 0) & (self.ids < ntotal)]] = True
+        return m
+
+
+IDSelectorArray = IDSelectorBatch
+
+
+class IDSelectorBitmap(IDSelector):
+    """A ready bitmap (uint8, bit i of the array = row i); rows past its end are not selected."""
+
+    def __init__(self, bitmap, *more):
+        if more:   # the SWIG spelling IDSelectorBitmap(n, bitmap)
+            bitmap = np.asarray(more[0], dtype=np.uint8).reshape(-1)[: int(bitmap)]
+        self.bits = np.ascontiguousarray(np.asarray(bitmap, dtype=np.uint8).reshape(-1))
+
+    def mask(self, ntotal: int) -> np.ndarray:
+        m = np.zeros(ntotal, dtype=np.bool_)
+        have = np.unpackbits(self.bits, bitorder="little")[:ntotal]
+        m[: have.shape[0]] = have != 0
+        return m
+
+
+class IDSelectorNot(IDSelector):
+    def __init__(self, sel: IDSelector):
+        self.sel = sel
+
+    def mask(self, ntotal: int) -> np.ndarray:
+        return ~self.sel.mask(ntotal)
+
+
+class IDSelectorAll(IDSelector):
+    def mask(self, ntotal: int) -> np.ndarray:
+        return np.ones(ntotal, dtype=np.bool_)
+
+
+class SearchParameters:
+    """faiss.SearchParameters(sel=...): the one field a flat index has."""
+
+    def __init__(self, sel=None):
+        self.sel = sel
+
+
+def _selector_of(params, ntotal: int):
+    """params (None | SearchParameters) -> what MipsIndex takes as selector=: the host bitmap of a shim selector; a
+    ram.Selector or a bool mask placed in params.sel passes through."""
+    sel = None if params is None else getattr(params, "sel", None)
+    if sel is None:
+        return None
+    return sel.bitmap(ntotal) if isinstance(sel, IDSelector) else sel
+
+
+def _no_other_keywords(what: str, kwargs: dict) -> None:
+    if kwargs:
+        raise TypeError(f"{what}() got an unexpected keyword argument {sorted(kwargs)[0]!r} (params= is the one it takes)")
+
+
 class IndexFlat:
     """faiss.IndexFlat(d, metric): d, ntotal, metric_type, is_trained, verbose, nprobe, add / train / search / range_search /
     reset."""
@@ -110,8 +201,10 @@ class IndexFlat:
             x = np.ascontiguousarray(x[:, :-1])
         self._index().add(x)
 
-    def search(self, x, k: int, **kwargs):
-        """(D float32 [nq, k], I int64 [nq, k]); NumPy in, NumPy out -- the call of mips.py:383-386 and of HF's search_batch."""
+    def search(self, x, k: int, params=None, **kwargs):
+        """(D float32 [nq, k], I int64 [nq, k]); NumPy in, NumPy out -- the call of mips.py:383-386 and of HF's search_batch.
+        params=SearchParameters(sel=IDSelector...) restricts the search to the selected rows (the filtered wide search)."""
+        _no_other_keywords("search", kwargs)
         ix = self._index()
         q = np.ascontiguousarray(x, dtype=np.float32)
         if self.metric_type == METRIC_L2:
@@ -123,13 +216,17 @@ class IndexFlat:
             q = np.ascontiguousarray(q[:, :-1])
         from .index import route_search
 
+        sel = _selector_of(params, ix.ntotal)
+        if sel is not None:
+            return route_search(ix, q, int(k), selector=sel)
         return route_search(ix, q, int(k))   # k > MAX_K: the wide search (k <= MAX_K_WIDE = 1024)
 
-    def range_search(self, x, thresh):
+    def range_search(self, x, thresh, params=None, **kwargs):
         """faiss Index.range_search(x, thresh) -> (lims uint64 [nq + 1], D float32, I int64): inner product, every row scoring
         strictly above thresh; L2 (queries prepared by augment_xq, as in search), every row whose augmented squared distance
         |q|^2 + phi - 2 q.x is strictly below it.  The hits of query j are D / I [lims[j] : lims[j + 1]], in ascending row order
-        (faiss leaves the order undefined).  NumPy in, NumPy out."""
+        (faiss leaves the order undefined).  NumPy in, NumPy out.  params=SearchParameters(sel=...): selected rows only."""
+        _no_other_keywords("range_search", kwargs)
         ix = self._index()
         q = np.ascontiguousarray(x, dtype=np.float32)
         if self.metric_type == METRIC_L2:
@@ -139,7 +236,8 @@ class IndexFlat:
                 raise ValueError("L2 range_search: the queries' last (augmentation) column is not zero; this index answers "
                                  "queries prepared by augment_xq (sotasum/mips.py:68-70)")
             q = np.ascontiguousarray(q[:, :-1])
-        lims, D, I = ix.range_search(q, thresh)
+        sel = _selector_of(params, ix.ntotal)
+        lims, D, I = ix.range_search(q, thresh) if sel is None else ix.range_search(q, thresh, selector=sel)
         return (np.asarray(lims).astype(np.uint64), np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(I, dtype=np.int64))
 
 

@@ -31,7 +31,12 @@ def _stream_handle(device: int) -> int:
 
 def route_search(index, q, k: int, **kwargs):
     """index.search(q, k), or index.search_wide(q, k) when k exceeds MAX_K and the index has a wide search (MipsIndex and
-    ShardedMipsIndex do; foreign duck-typed indexes keep their own search and its limits)."""
+    ShardedMipsIndex do; foreign duck-typed indexes keep their own search and its limits).  A call carrying selector= (a
+    filtered search) goes to search_wide whatever k is: search() itself has no selector."""
+    if "selector" in kwargs:
+        if kwargs["selector"] is not None:
+            return index.search_wide(q, int(k), **kwargs)
+        kwargs = {key: v for key, v in kwargs.items() if key != "selector"}
     if int(k) > _lib.MAX_K and hasattr(index, "search_wide"):
         return index.search_wide(q, int(k), **kwargs)
     return index.search(q, k, **kwargs)
@@ -212,14 +217,46 @@ class MipsIndex:
         del keep
         return D, I
 
-    def search_wide(self, x, k: int, idx_offset: int = 0, force_ip: bool = False):
+    def _sel_args(self, selector, sel_bit0: int, what: str):
+        """selector (None | Selector | bool mask | NumPy uint8 bitmap) -> (pointer, nbits, flag, keepalive) of the *_sel entry
+        points.  A Selector or a bool mask is a device bitmap; a NumPy uint8 array is passed as the host bitmap it is."""
+        import torch
+
+        from .selector import Selector
+
+        if selector is None:
+            return None, 0, 0, None
+        sel_bit0 = int(sel_bit0)
+        if sel_bit0 < 0:
+            raise ValueError(f"{what}: sel_bit0 must be >= 0")
+        if isinstance(selector, np.ndarray) and selector.dtype == np.uint8:
+            host = np.ascontiguousarray(selector.reshape(-1))
+            ptr, nbits, flag, keep = host.ctypes.data, 8 * host.shape[0], 0, host
+        else:
+            if not isinstance(selector, Selector):
+                if isinstance(selector, torch.Tensor) and selector.dtype == torch.uint8:
+                    selector = Selector.from_bitmap(selector, 8 * selector.numel(), device=self.device)
+                else:
+                    selector = Selector.from_mask(selector, device=self.device)
+            selector = selector.to(self.device)
+            bits = selector.bits.contiguous()
+            ptr, nbits, flag, keep = bits.data_ptr(), selector.nbits, _lib.SEL_DEVICE, bits
+        if nbits < sel_bit0 + self.ntotal:
+            raise ValueError(f"{what}: the selector has {nbits} bits; rows {sel_bit0} .. {sel_bit0 + self.ntotal} of it are needed")
+        return ptr, nbits, flag, keep
+
+    def search_wide(self, x, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, sel_bit0: int = 0):
         """search() for k up to MAX_K_WIDE = 1024 (mips_search_wide: threshold scan, streaming select, exact re-score; every
         query certified or settled exactly in the same call).  bf16 and f32 indexes of at most 1024 columns.  NumPy in ->
-        NumPy out; torch CUDA tensor in -> torch CUDA tensors out, stream-ordered, no synchronisation."""
+        NumPy out; torch CUDA tensor in -> torch CUDA tensors out, stream-ordered, no synchronisation.
+        selector (a Selector, a bool mask or a NumPy uint8 bitmap; one for all queries): only the selected rows can be results
+        -- what the search returns on an index from which the others were deleted, row numbers, phi and maximal norm kept;
+        fewer than k selected rows leave the -1 / -+inf padding.  Bit sel_bit0 + i of the selector decides local row i."""
         import torch
 
         k = int(k)
         self._check_wide(k)
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self._sel_args(selector, sel_bit0, "search_wide")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         stream = _stream_handle(self.device)
         if is_dev:
@@ -236,9 +273,13 @@ class MipsIndex:
         if force_ip:
             flags |= _lib.FORCE_IP
         with self._mutex:
-            _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags, stream),
-                       "mips_search_wide")
-        del keep
+            if selector is None:
+                _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags, stream),
+                           "mips_search_wide")
+            else:
+                _lib.check(self._lib.mips_search_wide_sel(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags | sel_flag,
+                                                          sel_ptr, sel_nbits, int(sel_bit0), stream), "mips_search_wide_sel")
+        del keep, sel_keep
         return D, I
 
     def _check_wide(self, k: int) -> None:
@@ -271,14 +312,15 @@ class MipsIndex:
             raise ValueError("range_search: a radius is NaN")
         return r
 
-    def range_search_into(self, x, radius, lims, D, I, idx_offset: int = 0, force_ip: bool = False) -> None:
+    def range_search_into(self, x, radius, lims, D, I, idx_offset: int = 0, force_ip: bool = False, selector=None) -> None:
         """The non-synchronising form of range_search: the caller allocates the CUDA tensors lims (int64 [nq + 1]), D (float32
         [cap]) and I (int64 [cap]); everything is enqueued on the current stream.  lims always receives the true counts; when
         lims[-1] > cap the contents of D and I are unspecified and the call is to be repeated with larger tensors.  cap = 0
-        (empty D and I) is a counting call.  `radius` is host data (a scalar or nq values)."""
+        (empty D and I) is a counting call.  `radius` is host data (a scalar or nq values).  selector: as in search_wide."""
         import torch
 
         self._check_range()
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self._sel_args(selector, 0, "range_search")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         r = self._radii(radius, nq)
         dev = torch.device("cuda", self.device)
@@ -290,22 +332,34 @@ class MipsIndex:
         cap = int(D.shape[0])
         flags = _lib.OUT_DEVICE | (_lib.Q_DEVICE if is_dev else 0) | (_lib.FORCE_IP if force_ip else 0)
         with self._mutex:
-            _lib.check(self._lib.mips_range_search(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
-                                                   D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
-                                                   int(idx_offset), flags, _stream_handle(self.device)), "mips_range_search")
-        del keep
+            if selector is None:
+                _lib.check(self._lib.mips_range_search(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
+                                                       D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
+                                                       int(idx_offset), flags, _stream_handle(self.device)), "mips_range_search")
+            else:
+                _lib.check(self._lib.mips_range_search_sel(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
+                                                           D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
+                                                           int(idx_offset), flags | sel_flag, sel_ptr, sel_nbits, 0,
+                                                           _stream_handle(self.device)), "mips_range_search_sel")
+        del keep, sel_keep
 
-    def range_search(self, x, radius, idx_offset: int = 0, force_ip: bool = False):
+    def range_search(self, x, radius, idx_offset: int = 0, force_ip: bool = False, selector=None):
         """faiss Index.range_search(x, radius) -> (lims, D, I): every stored row whose canonical score is strictly above the
         radius (inner product; L2: whose distance |q|^2 + phi - 2 q.x is strictly below it).  `radius` is a scalar or nq
         values.  The hits of query j are D / I [lims[j] : lims[j + 1]], in ascending row order; lims is int64 [nq + 1].
         NumPy in -> NumPy out; torch CUDA tensor in -> torch CUDA tensors out.  The result's size is not known beforehand: a
         first call runs with a guessed capacity, lims[-1] is READ ON THE HOST -- THIS SYNCHRONISES the stream -- and one repeat
         with the exact size follows if the guess was too small (range_search_into is the form that never synchronises).
-        bf16 and f32 indexes of at most 1024 columns."""
+        bf16 and f32 indexes of at most 1024 columns.  selector (as in search_wide): only selected rows can be hits."""
         import torch
 
+        from .selector import Selector
+
         self._check_range()
+        if selector is not None and not isinstance(selector, (Selector, np.ndarray)):
+            selector = Selector.from_mask(selector, device=self.device)   # packed once for the repeat call
+        if isinstance(selector, np.ndarray) and selector.dtype != np.uint8:
+            selector = Selector.from_mask(selector, device=self.device)
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         r = self._radii(radius, nq)
         dev = f"cuda:{self.device}"
@@ -314,7 +368,7 @@ class MipsIndex:
         while True:
             D = torch.empty(cap, dtype=torch.float32, device=dev)
             I = torch.empty(cap, dtype=torch.int64, device=dev)
-            self.range_search_into(keep, r, lims, D, I, idx_offset=idx_offset, force_ip=force_ip)
+            self.range_search_into(keep, r, lims, D, I, idx_offset=idx_offset, force_ip=force_ip, selector=selector)
             total = int(lims[-1].item())   # the synchronisation
             if total <= cap:
                 break
@@ -324,22 +378,29 @@ class MipsIndex:
             return lims, D.clone() if total < cap else D, I.clone() if total < cap else I
         return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
 
-    def search_wide_packed(self, x, k: int, idx_offset: int = 0, force_ip: bool = False):
+    def search_wide_packed(self, x, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, sel_bit0: int = 0):
         """Device-only search_wide returning the all-gather payload: CUDA int64 [nq, k, 2] = {float32 score bits,
-        index + idx_offset}, row for row what search_wide returns (padding included)."""
+        index + idx_offset}, row for row what search_wide returns (padding included).  selector / sel_bit0 as in search_wide:
+        a row shard passes the global selector and its first global row."""
         import torch
 
         k = int(k)
         self._check_wide(k)
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self._sel_args(selector, sel_bit0, "search_wide_packed")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         if not is_dev:
             raise ValueError("search_wide_packed needs a CUDA tensor")
         out = torch.empty((nq, k, 2), dtype=torch.int64, device=f"cuda:{self.device}")
         flags = _lib.Q_DEVICE | _lib.OUT_DEVICE | _lib.OUT_PACKED | (_lib.FORCE_IP if force_ip else 0)
         with self._mutex:
-            _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, None, out.data_ptr(), int(idx_offset), flags,
-                                                  _stream_handle(self.device)), "mips_search_wide")
-        del keep
+            if selector is None:
+                _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, None, out.data_ptr(), int(idx_offset), flags,
+                                                      _stream_handle(self.device)), "mips_search_wide")
+            else:
+                _lib.check(self._lib.mips_search_wide_sel(self._h, ptr, code, nq, k, None, out.data_ptr(), int(idx_offset),
+                                                          flags | sel_flag, sel_ptr, sel_nbits, int(sel_bit0),
+                                                          _stream_handle(self.device)), "mips_search_wide_sel")
+        del keep, sel_keep
         return out
 
     def search_fused(self, x, k: int, normalize: bool = False, ignore=None, idx_offset: int = 0):

@@ -313,13 +313,15 @@ class KnowledgeBase:
         order = np.lexsort((j, i))
         return i[order], j[order], s[order]
 
-    def get_nearest_examples_batch(self, index_name: str, queries, k: int = 10):
+    def get_nearest_examples_batch(self, index_name: str, queries, k: int = 10, selector=None):
         """HF Dataset.get_nearest_examples_batch as used at retriever_lightning.py:317-321: returns (scores
         per query, examples per query as dict of columns); ids < 0 are dropped like datasets/search.py does.
-        L2 indexes take the reference's augmented queries ([B, d + 1], zero last column) as they come."""
+        L2 indexes take the reference's augmented queries ([B, d + 1], zero last column) as they come.
+        selector (ram.Selector, bool mask or NumPy bitmap over the rows): only selected rows are retrieved -- one partition of
+        a knowledge base, an `aid` group, everything but a cluster of near duplicates."""
         index = self.get_index(index_name).faiss_index
         q = _strip_augmentation_column(index, np.asarray(queries, dtype=np.float32))
-        s, i = route_search(index, np.ascontiguousarray(q), k)
+        s, i = route_search(index, np.ascontiguousarray(q), k, **({} if selector is None else {"selector": selector}))
         scores, examples = [], []
         for row_s, row_i in zip(s, i):
             keep = row_i >= 0

@@ -288,13 +288,15 @@ class ShardedMipsIndex:
         return ShardedMipsIndex._Pending(out, done, (packed, gathered, q), self.local)
 
     # ------------------------------------------------------------------ search
-    def search(self, q, k: int, idx_offset: int = 0, force_ip: bool = False):
+    def search(self, q, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None):
         """Replicated queries in, global top-k out (same on every rank).  force_ip: rank by inner product on an
         L2 index (Mips.np_search); idx_offset exists for signature compatibility with MipsIndex.search and must
-        be 0 (global row numbers are the shard offsets' business)."""
+        be 0 (global row numbers are the shard offsets' business).  selector: a filtered search, served by search_wide."""
         import torch
         import torch.distributed as dist
 
+        if selector is not None:
+            return self.search_wide(q, k, idx_offset=idx_offset, force_ip=force_ip, selector=selector)
         if idx_offset:
             raise ValueError("ShardedMipsIndex.search returns global row numbers; idx_offset must be 0")
         if force_ip:
@@ -317,14 +319,26 @@ class ShardedMipsIndex:
         s, i = self._local_search(q, k, self.lo)
         return self._exchange(s, i, k, self.metric_type)
 
-    def search_wide(self, q, k: int, idx_offset: int = 0, force_ip: bool = False):
+    def search_wide(self, q, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None):
         """search() for k up to MAX_K_WIDE = 1024 (route_search sends k > MAX_K here): every shard runs MipsIndex.search_wide,
         then the same ONE all-gather, then the merge for sorted lists (mips_merge_topk_sorted_packed: the counting merge of
         search() is quadratic in world * k).  bf16 and f32 shards of at most 1024 columns; idx_offset must be 0; force_ip as in
         search().  Every query is certified or settled on its shard, so margin_stats() reports unresolved = 0.  The payload is
-        nq * k * 16 bytes per rank -- bandwidth- rather than latency-sized -- and the gathered buffer `world` times that."""
+        nq * k * 16 bytes per rank -- bandwidth- rather than latency-sized -- and the gathered buffer `world` times that.
+        selector: a GLOBAL selector (one bit per global row, the same on every rank; Selector, bool mask or NumPy bitmap); each
+        shard reads its own rows' bits from bit `lo` on, the exchange and the merge are those of the unfiltered search."""
         import torch
         import torch.distributed as dist
+
+        sel_kw = {}
+        if selector is not None:
+            from .selector import Selector
+
+            nbits = selector.nbits if isinstance(selector, Selector) else (
+                8 * selector.size if isinstance(selector, np.ndarray) and selector.dtype == np.uint8 else len(selector))
+            if nbits < self.ntotal_global:
+                raise ValueError(f"search_wide: the selector has {nbits} bits, the sharded index {self.ntotal_global} rows")
+            sel_kw = {"selector": selector, "sel_bit0": self.lo}
 
         if idx_offset:
             raise ValueError("ShardedMipsIndex.search_wide returns global row numbers; idx_offset must be 0")
@@ -338,7 +352,7 @@ class ShardedMipsIndex:
             # device fast path, as in search(): the shard's result leaves as the payload, the merge reads it as it arrives
             from .index import merge_topk_sorted_packed
 
-            packed = self.local.search_wide_packed(q, k, self.lo, force_ip=force_ip)
+            packed = self.local.search_wide_packed(q, k, self.lo, force_ip=force_ip, **sel_kw)
             nq = packed.shape[0]
             if dist.get_backend(self.group) == "gloo":
                 packed = packed.cpu()
@@ -347,7 +361,7 @@ class ShardedMipsIndex:
             if not gathered.is_cuda:
                 gathered = gathered.to(q.device)
             return merge_topk_sorted_packed(gathered, nq, self.world, k, metric)
-        s, i = self._local_search_wide(q, k, self.lo, **({"force_ip": True} if force_ip else {}))
+        s, i = self._local_search_wide(q, k, self.lo, **({"force_ip": True} if force_ip else {}), **sel_kw)
         return self._exchange(s, i, k, metric)
 
     def _search_force_ip(self, q, k: int):
