@@ -60,6 +60,12 @@ extern "C" {
 #define MIPS_OUT_PACKED 4 /* with MIPS_OUT_DEVICE: out_idx receives [nq, k, 2] int64 = {float32 score bits
                              (zero-extended), index}, the all-gather payload; out_scores is ignored */
 #define MIPS_SEL_DEVICE 16 /* mips_search_wide_sel / mips_range_search_sel: sel_bits is device memory */
+#define MIPS_GRP_DEVICE 32 /* mips_search_wide_grp / mips_range_search_grp: q_labels is device memory */
+
+/* group filters (mips_search_wide_grp / mips_range_search_grp) */
+#define MIPS_GRP_EXCLUDE 0 /* row i may answer query j iff label[i] != q_labels[j] */
+#define MIPS_GRP_ONLY 1    /* row i may answer query j iff label[i] == q_labels[j] */
+#define MIPS_LABEL_NONE INT32_MIN /* as a query's label: the query is not group-filtered (either mode); as a row's: a group no query can name */
 
 /* synthetic data kinds (same functions as oracle/synth.py) */
 #define MIPS_SYNTH_LATTICE 0
@@ -248,6 +254,40 @@ int mips_search_wide_sel(mips_index_t* index, const void* q, int q_dtype, int64_
 int mips_range_search_sel(mips_index_t* index, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
                           float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags,
                           const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream);
+
+/* PER-QUERY GROUP FILTERS for the wide top-k and the range search.  The index stores one int32 label per row, a grouped call passes
+ * one int32 label per query and a mode: under MIPS_GRP_EXCLUDE row i may answer query j iff label[i] != q_labels[j] (leak-free
+ * retrieval, hard negatives: "the best k rows that are NOT of my article"), under MIPS_GRP_ONLY iff label[i] == q_labels[j]
+ * (retrieval inside a group).  A query labelled MIPS_LABEL_NONE is not filtered.  The reference's only filter drops ONE row id per
+ * query from a k + 1 fetch (`ignore_indexes`, sotasum/mips.py:382-400); a group has no bounded size, so no k + m fetch replaces this.
+ *
+ * mips_index_set_labels writes the labels of rows [row0, row0 + n) from host or device memory (src_is_device).  The labelled rows
+ * are a prefix of the index: row0 + n <= ntotal and row0 <= (rows labelled so far), anything else is MIPS_E_INVALID, so a build
+ * that adds in batches labels as it goes and may rewrite what it labelled.  The labels live in library storage next to the rows,
+ * survive mips_index_reserve and growth, and are cleared by mips_index_reset.  mips_index_read_labels copies labels of labelled rows
+ * to the host (it synchronises the stream).
+ *
+ * The grouped searches take the parameters of the _sel calls, then q_labels (int32 [nq], host or device: MIPS_GRP_DEVICE) and
+ * grp_mode.  The bitmap is optional (sel_bits == NULL: none) and applies on top: a row is admitted for query j iff its bit is set
+ * AND the group rule holds.  The result for query j is what the unfiltered call returns for j on an index from which the rows not
+ * admitted for j were deleted, row numbers, phi and maximal norm kept -- the definition of the _sel calls, per query; score, order,
+ * strict range rule, padding, idx_offset, MIPS_FORCE_IP, MIPS_OUT_PACKED, served storages and limits are theirs too.
+ * q_labels == NULL IS the _sel call: same path, same kernels, same bits.  A grouped call on an index whose labelled prefix is not
+ * exactly ntotal (never labelled, rows added since) and a grp_mode other than 0 / 1 are MIPS_E_INVALID.
+ * How: the threshold scan runs as its grouped instance (mips_index_last_kernel: "mips::grouped_scan_kernel"), which tests the group
+ * rule where it appends a row; the certificate treats a pool short of k' entries as the query's whole admitted set and checks a
+ * full pool against the bound as ever; the exact settlement tests the rule per (query, row) (DESIGN.md "Grouped search").  Every
+ * grouped wide search is certified or settled in the call (unresolved = 0), a grouped range search reports 0 / 0 / 0.  Device-output
+ * calls never synchronise: host q_labels travel by the stream's asynchronous copy (they must stay valid until the call returns). */
+int mips_index_set_labels(mips_index_t* index, const int32_t* labels, int64_t row0, int64_t n, int src_is_device, void* hip_stream);
+int mips_index_read_labels(mips_index_t* index, int64_t row0, int64_t n, int32_t* out_host, void* hip_stream);
+int mips_search_wide_grp(mips_index_t* index, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                         int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0,
+                         const int32_t* q_labels, int grp_mode, void* hip_stream);
+int mips_range_search_grp(mips_index_t* index, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
+                          float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags,
+                          const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels, int grp_mode,
+                          void* hip_stream);
 
 /* The device-resident scoring hook in one call: what retriever_generator.py:143-153 -> mips.py:421-422 does per
  * training / generation step -- `_prepare_query` (row normalisation for the normalised inner-product index,

@@ -23,7 +23,9 @@ ABI_VERSION = 1
 # constants of include/mips_hip.h
 DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3, DTYPE_FP8_E4M3_DOCS = 0, 1, 2, 3
 METRIC_IP, METRIC_L2 = 0, 1
-Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP, SEL_DEVICE = 1, 2, 4, 8, 16
+Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP, SEL_DEVICE, GRP_DEVICE = 1, 2, 4, 8, 16, 32
+GRP_EXCLUDE, GRP_ONLY = 0, 1  # MIPS_GRP_*: the mode of a grouped search
+LABEL_NONE = -(1 << 31)  # MIPS_LABEL_NONE = INT32_MIN: a query that is not group-filtered
 SYNTH_LATTICE, SYNTH_GAUSS, SYNTH_LATTICE_FP8 = 0, 1, 2
 SEED_DOCS, SEED_QUERIES = 0xD0C5, 0x0E21  # fixed seeds of the synthetic workloads
 MAX_K = 29
@@ -110,6 +112,10 @@ def _bind(lib):
         "mips_range_search": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, i64, i32, vp]),
         "mips_search_wide_sel": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, i64, i64, vp]),
         "mips_range_search_sel": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, i64, i32, vp, i64, i64, vp]),
+        "mips_index_set_labels": (i32, [vp, vp, i64, i64, i32, vp]),
+        "mips_index_read_labels": (i32, [vp, i64, i64, vp, vp]),
+        "mips_search_wide_grp": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, i64, i64, vp, i32, vp]),
+        "mips_range_search_grp": (i32, [vp, vp, i32, i64, vp, vp, vp, vp, i64, i64, i32, vp, i64, i64, vp, i32, vp]),
         "mips_search_split": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, vp]),
         "mips_search_fused": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp, i64, vp]),
         "mips_merge_topk": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, i32, vp]),
@@ -144,6 +150,7 @@ EXPORTS = (
     "mips_index_check_error", "mips_index_last_kernel", "mips_cosine_rescore_backward", "mips_index_margin_stats", "mips_search_fused", "mips_search_split",
     "mips_rows_max_sumsq_device", "mips_search_wide", "mips_merge_topk_sorted_packed", "mips_range_search",
     "mips_search_wide_sel", "mips_range_search_sel",
+    "mips_index_set_labels", "mips_index_read_labels", "mips_search_wide_grp", "mips_range_search_grp",
 )
 
 

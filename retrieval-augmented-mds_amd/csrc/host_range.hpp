@@ -10,7 +10,9 @@ static_assert(kWideSlice == 4 * mips::RANGE_LIMS_THREADS, "range_lims_kernel tak
 // d_lims [nq + 1], d_s / d_i [cap] are DEVICE buffers; radii is the caller's HOST array.  nq > 0 and ntotal > 0.
 int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* d_lims, float* d_s, int64_t* d_i, int64_t cap,
                  int64_t idx_offset, bool q_dev, Selector sel, hipStream_t st) {
-    const bool masked = sel.bits != nullptr; // a filtered search: only the scan changes, the filter sees appended rows alone
+    // a filtered or grouped search: only the scan changes, the filter sees appended rows alone
+    const bool grouped = sel.qlab != nullptr;
+    const bool masked = sel.bits != nullptr && !grouped;
     const bool f32x = ix->plane > 0;
     const bool l2 = ix->call_metric == MIPS_METRIC_L2;
     const int sld = f32x ? ix->hp : ix->ld;    // row pitch of the scanned bf16 rows
@@ -68,9 +70,10 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
     const size_t qesz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
     const double err_c = (double)ix->d * 1.1920928955078125e-07 * (f32x ? 1.01 : 1.0);
     const int scan_lds = mips::SCAN_LDS_BYTES;
-    if (masked) {
-        HIP_TRY(hipFuncSetAttribute((const void*)mips::masked_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
-        rc = stage_selector(ix, sel, st);
+    if (grouped || masked) {
+        const void* scan = grouped ? (const void*)mips::grouped_scan_kernel : (const void*)mips::masked_scan_kernel;
+        HIP_TRY(hipFuncSetAttribute(scan, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+        rc = stage_selector(ix, sel, nq, st);
         if (rc) return rc;
     } else {
         HIP_TRY(hipFuncSetAttribute((const void*)mips::wide_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
@@ -144,6 +147,9 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
         sa.cnt = (int*)ix->w_cnt.p;
         sa.tiles_per_split = tps;
         sa.sel = sel.words;
+        sa.rlab = ix->labels;
+        sa.qlab = grouped ? sel.qlab_staged + s0 : nullptr; // (s0 is a multiple of the query tile)
+        sa.grp_only = sel.grp_only;
         mips::RangeFilterArgs fa;
         fa.seg = sa.seg;
         fa.nseg = nseg;
@@ -168,7 +174,8 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
             sa.tile_end = (int)std::min<int64_t>(ntiles, sa.tile0 + chunk_tiles);
             fa.row0 = sa.tile0 * mips::TM;
             fa.chunk = chunk;
-            if (masked) mips::masked_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            if (grouped) mips::grouped_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            else if (masked) mips::masked_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
             else mips::wide_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
             if (f32x) {
                 if (l2) mips::range_filter_kernel<mips::ElemF32, true><<<(int)ns, mips::RANGE_THREADS, 0, st>>>(fa);
@@ -207,7 +214,7 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
         }
         HIP_TRY(hipGetLastError());
     }
-    set_kernel_name(ix, masked ? "mips::masked_scan_kernel" : "mips::wide_scan_kernel");
+    set_kernel_name(ix, grouped ? "mips::grouped_scan_kernel" : masked ? "mips::masked_scan_kernel" : "mips::wide_scan_kernel");
     return MIPS_OK;
 }
 

@@ -144,6 +144,12 @@ struct mips_index {
     // filtered searches (mips_search_wide_sel / mips_range_search_sel): the device copy of a host bitmap, and the staged selector
     // ([0] the number of selected rows, from byte 16 on four 32-bit words per 128-row tile; select_kernels.hpp)
     Buffer sel_raw, sel_words;
+    // grouped searches (mips_search_wide_grp / mips_range_search_grp): one int32 label per row in storage of its own, allocated in
+    // whole 128-row tiles for at least `capacity` rows (mips_index_set_labels grows it and keeps what it held, so it survives the
+    // growth of the rows); rows [0, nlabelled) carry a label.  grp_q: the staged per-query labels of the call in flight.
+    int* labels = nullptr;
+    int64_t labels_cap = 0, nlabelled = 0;
+    Buffer grp_q;
     int opt_resolve = 1; // flagged queries: 1 = exact brute-force resolution (resolve_kernels.hpp; 2 = its plain form, no MFMA pre-filter), 0 = re-scan with the widest lists
     int resolve_budget = 0; // "resolve_budget" > 0: flagged queries a search resolves at most (0 = RESOLVE_MAX); a search that flags
                             // more keeps its first results (counted unresolved) -- or, if its first scan was an optimistic one,

@@ -9,6 +9,7 @@ constexpr int64_t kWideBudget = 1ll << 25;   // segment entries (8 bytes each): 
 constexpr int64_t kWideSlice = 4096;         // queries per slice
 constexpr int64_t kWideMaxChunkRows = 1 << 17;
 constexpr int kWideExactSlots = 256;         // flagged queries one settlement round takes
+static_assert(kWideSlice % mips::TN == 0, "a slice reads the staged query labels at its offset: whole query tiles");
 
 // k' - k.  The pool must reach past the k-th result by the error of the scores that selected it: d 2^-23 |q| max|x| on a bf16
 // index (a few ranks on Gaussian data), the representation error of bf16(x) . bf16(q) on the fp32-exact index (~0.1 sigma:
@@ -34,11 +35,18 @@ struct Selector {
     bool dev = false;                          // bits is device memory (MIPS_SEL_DEVICE)
     const unsigned* words = nullptr;           // staged: four words per 128-row tile
     const unsigned long long* nsel = nullptr;  // staged: number of selected rows
+    // a grouped call (qlab != nullptr): one label per query, tested against the index's row labels
+    const int32_t* qlab = nullptr;
+    bool qlab_dev = false;                     // qlab is device memory (MIPS_GRP_DEVICE)
+    int grp_only = 0;                          // MIPS_GRP_ONLY
+    const int* qlab_staged = nullptr;          // staged: [round_up(nq, TN)], MIPS_LABEL_NONE behind the caller's nq
 };
 
 // Runs once per call, before the first slice: the bitmap (a host one is copied with the stream's async copy) becomes the
 // shifted, cleared and padded words of select_kernels.hpp, and their popcount.  Nothing is read back.
-int stage_selector(mips_index* ix, Selector& sel, hipStream_t st) {
+// A grouped call without a bitmap stages all ones over [0, ntotal), and every grouped call stages its query labels: a slice reads
+// them at its offset (a multiple of the query tile), the last one up to the pad.
+int stage_selector(mips_index* ix, Selector& sel, int64_t nq, hipStream_t st) {
     const int64_t ntiles = (ix->ntotal + mips::TM - 1) / mips::TM;
     const int64_t nwords = ntiles * (mips::TM / 32);
     int rc = ix->sel_words.ensure(16 + (size_t)nwords * sizeof(unsigned));
@@ -46,7 +54,10 @@ int stage_selector(mips_index* ix, Selector& sel, hipStream_t st) {
     const uint8_t* src = sel.bits;
     int64_t bit0 = sel.bit0;
     int64_t nbytes = (sel.nbits + 7) >> 3;
-    if (!sel.dev) { // only the bytes that hold bits bit0 .. bit0 + ntotal - 1 travel
+    if (sel.bits == nullptr) {
+        bit0 = 0;
+        nbytes = 0;
+    } else if (!sel.dev) { // only the bytes that hold bits bit0 .. bit0 + ntotal - 1 travel
         const int64_t b0 = sel.bit0 >> 3, b1 = (sel.bit0 + ix->ntotal + 7) >> 3;
         rc = ix->sel_raw.ensure((size_t)(b1 - b0));
         if (rc) return rc;
@@ -62,14 +73,26 @@ int stage_selector(mips_index* ix, Selector& sel, hipStream_t st) {
     HIP_TRY(hipGetLastError());
     sel.words = words;
     sel.nsel = nsel;
+    if (sel.qlab != nullptr) {
+        const int64_t nq_pad = round_up(nq, mips::TN);
+        rc = ix->grp_q.ensure((size_t)nq_pad * sizeof(int));
+        if (rc) return rc;
+        int* ql = (int*)ix->grp_q.p;
+        HIP_TRY(hipMemcpyAsync(ql, sel.qlab, (size_t)nq * sizeof(int), sel.qlab_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        if (nq_pad > nq) mips::label_pad_kernel<<<(int)((nq_pad - nq + 127) / 128), 128, 0, st>>>(ql, nq, nq_pad);
+        HIP_TRY(hipGetLastError());
+        sel.qlab_staged = ql;
+    }
     return MIPS_OK;
 }
 
 // packed: d_i is the MIPS_OUT_PACKED payload [nq][k][2] and d_s is not written (it may be NULL)
 // sel.bits != nullptr: a filtered search (masked scan, certificate on the selected count, masked settlement)
+// sel.qlab != nullptr: a grouped search (grouped scan, certificate without a count, settlement that tests the labels)
 int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool q_dev,
                 Selector sel, hipStream_t st) {
-    const bool masked = sel.bits != nullptr;
+    const bool grouped = sel.qlab != nullptr;
+    const bool masked = sel.bits != nullptr && !grouped;
     const bool f32x = ix->plane > 0;
     const bool l2 = ix->call_metric == MIPS_METRIC_L2;
     const int sld = f32x ? ix->hp : ix->ld;    // row pitch of the scanned bf16 rows
@@ -139,9 +162,10 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
     const size_t qesz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
     const double err_c = (double)ix->d * 1.1920928955078125e-07 * (f32x ? 1.01 : 1.0);
     const int scan_lds = mips::SCAN_LDS_BYTES;
-    if (masked) {
-        HIP_TRY(hipFuncSetAttribute((const void*)mips::masked_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
-        rc = stage_selector(ix, sel, st);
+    if (grouped || masked) {
+        const void* scan = grouped ? (const void*)mips::grouped_scan_kernel : (const void*)mips::masked_scan_kernel;
+        HIP_TRY(hipFuncSetAttribute(scan, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
+        rc = stage_selector(ix, sel, nq, st);
         if (rc) return rc;
     } else {
         HIP_TRY(hipFuncSetAttribute((const void*)mips::wide_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, scan_lds));
@@ -152,6 +176,7 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         const int64_t ns_pad = round_up(ns, mips::TN);
         const int nqt = (int)(ns_pad / mips::TN);
         const void* qs = (const char*)q + (size_t)s0 * ix->d * qesz;
+        const int* qlab_s = grouped ? sel.qlab_staged + s0 : nullptr; // (s0 is a multiple of the query tile)
         float* out_s = packed ? nullptr : d_s + (size_t)s0 * k;
         int64_t* out_i = packed ? nullptr : d_i + (size_t)s0 * k;
         int64_t* out_packed = packed ? d_i + (size_t)s0 * k * 2 : nullptr;
@@ -196,6 +221,9 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         sa.segcap = segcap;
         sa.cnt = w.cnt;
         sa.sel = sel.words;
+        sa.rlab = ix->labels;
+        sa.qlab = qlab_s;
+        sa.grp_only = sel.grp_only;
         mips::WideSelArgs se;
         se.seg = sa.seg;
         se.nseg = nseg;
@@ -216,7 +244,8 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
             sa.tile0 = (int)tile;
             sa.tile_end = (int)std::min<int64_t>(ntiles, tile + (int64_t)tps * nsplit);
             sa.tiles_per_split = tps;
-            if (masked) mips::masked_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            if (grouped) mips::grouped_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
+            else if (masked) mips::masked_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
             else mips::wide_scan_kernel<<<nqt * nsplit, mips::SCAN_THREADS, scan_lds, st>>>(sa);
             mips::wide_select_kernel<<<(int)ns, mips::WIDE_THREADS, 0, st>>>(se);
             HIP_TRY(hipGetLastError());
@@ -248,7 +277,15 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         ra.qerr2 = f32x ? (const double*)ix->qerr2.p : nullptr;
         ra.err_c = err_c;
         ra.nsel = sel.nsel;
-        if (masked) {
+        if (grouped) {
+            if (f32x) {
+                if (l2) mips::wide_rescore_kernel<mips::ElemF32, true, true, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+                else mips::wide_rescore_kernel<mips::ElemF32, false, true, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+            } else {
+                if (l2) mips::wide_rescore_kernel<mips::ElemBF16, true, true, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+                else mips::wide_rescore_kernel<mips::ElemBF16, false, true, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
+            }
+        } else if (masked) {
             if (f32x) {
                 if (l2) mips::wide_rescore_kernel<mips::ElemF32, true, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
                 else mips::wide_rescore_kernel<mips::ElemF32, false, true><<<(int)ns, mips::WIDE_THREADS, 0, st>>>(ra);
@@ -292,6 +329,9 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         xa.out_i = out_i;
         xa.out_packed = out_packed;
         xa.sel = sel.words;
+        xa.rlab = ix->labels;
+        xa.qlab = qlab_s;
+        xa.grp_only = sel.grp_only;
         mips::WideSelArgs xe = se;
         xe.nseg = 1;
         xe.segcap = (int)xrows;
@@ -313,7 +353,9 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
                 xa.r0 = r0;
                 xa.r1 = std::min(ix->ntotal, r0 + xrows);
                 const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(512, (xa.r1 - xa.r0 + 511) / 512));
-                if (masked && f32x) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemF32, true, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemF32, false, true>, grid);
+                if (grouped && f32x) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemF32, true, true, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemF32, false, true, true>, grid);
+                else if (grouped) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemBF16, true, true, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemBF16, false, true, true>, grid);
+                else if (masked && f32x) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemF32, true, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemF32, false, true>, grid);
                 else if (masked) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemBF16, true, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemBF16, false, true>, grid);
                 else if (f32x) rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemF32, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemF32, false>, grid);
                 else rc = l2 ? producer(mips::wide_exact_kernel<mips::ElemBF16, true>, grid) : producer(mips::wide_exact_kernel<mips::ElemBF16, false>, grid);
@@ -325,7 +367,7 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
             HIP_TRY(hipGetLastError());
         }
     }
-    set_kernel_name(ix, masked ? "mips::masked_scan_kernel" : "mips::wide_scan_kernel");
+    set_kernel_name(ix, grouped ? "mips::grouped_scan_kernel" : masked ? "mips::masked_scan_kernel" : "mips::wide_scan_kernel");
     // statistics: flagged = settled exactly; nothing is ever left unresolved
     ix->last_flagged = -1; // (on the device: mips_index_margin_stats fetches the two words when asked)
     ix->last_rescanned = 0;

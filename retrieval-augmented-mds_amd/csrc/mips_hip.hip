@@ -150,6 +150,8 @@ int mips_index_destroy(mips_index_t* ix) {
     ix->r_lims.release();
     ix->sel_raw.release();
     ix->sel_words.release();
+    ix->grp_q.release();
+    if (ix->labels) (void)hipFree(ix->labels);
     for (int e = 0; e < mips_index::kEvRing; ++e) {
         if (ix->ev0[e]) (void)hipEventDestroy(ix->ev0[e]);
         if (ix->ev1[e]) (void)hipEventDestroy(ix->ev1[e]);
@@ -204,11 +206,59 @@ int mips_index_add(mips_index_t* ix, const void* rows, int64_t n, int src_dtype,
 int mips_index_reset(mips_index_t* ix) {
     if (!ix) return fail(MIPS_E_INVALID, "mips_index_reset: index is NULL");
     ix->ntotal = 0;
+    ix->nlabelled = 0;
     ix->hi_rows = 0;
     ix->phi_valid = false;
     ix->phi_override = false;
     ix->xmax2_valid = false;
     ix->dres2_valid = false;
+    return MIPS_OK;
+}
+
+int mips_index_set_labels(mips_index_t* ix, const int32_t* labels, int64_t row0, int64_t n, int src_is_device, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "mips_index_set_labels: index is NULL");
+    if (row0 < 0 || n < 0 || (n > 0 && !labels) || row0 + n > ix->ntotal)
+        return fail(MIPS_E_INVALID, "mips_index_set_labels: bad range [%lld, +%lld) of %lld rows", (long long)row0, (long long)n, (long long)ix->ntotal);
+    if (row0 > ix->nlabelled)
+        return fail(MIPS_E_INVALID, "mips_index_set_labels: row0 = %lld leaves a gap behind the %lld labelled rows", (long long)row0,
+                    (long long)ix->nlabelled);
+    if (n == 0) return MIPS_OK;
+    DeviceGuard g(ix->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st);
+    const int64_t need = round_up(std::max(ix->capacity, ix->ntotal), mips::TM); // whole tiles: the grouped scan loads a tile's labels
+    if (ix->labels_cap < need) {
+        int* fresh = nullptr;
+        hipError_t e = hipMalloc((void**)&fresh, (size_t)need * sizeof(int));
+        if (e != hipSuccess) return fail(MIPS_E_NOMEM, "hipMalloc(%zu) for the row labels failed: %s", (size_t)need * sizeof(int), hipGetErrorString(e));
+        e = hipMemsetAsync(fresh, 0, (size_t)need * sizeof(int), st);
+        if (e == hipSuccess && ix->nlabelled > 0)
+            e = hipMemcpyAsync(fresh, ix->labels, (size_t)ix->nlabelled * sizeof(int), hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess && ix->labels) e = hipStreamSynchronize(st); // the old storage is freed below
+        if (e != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(MIPS_E_HIP, "growing the row labels to %lld rows failed: %s", (long long)need, hipGetErrorString(e));
+        }
+        if (ix->labels) (void)hipFree(ix->labels);
+        ix->labels = fresh;
+        ix->labels_cap = need;
+    }
+    HIP_TRY(hipMemcpyAsync(ix->labels + row0, labels, (size_t)n * sizeof(int), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if (!src_is_device) HIP_TRY(hipStreamSynchronize(st)); // the caller's array may go once the call returns
+    ix->nlabelled = std::max(ix->nlabelled, row0 + n);
+    return MIPS_OK;
+}
+
+int mips_index_read_labels(mips_index_t* ix, int64_t row0, int64_t n, int32_t* out_host, void* hip_stream) {
+    if (!ix || row0 < 0 || n < 0 || row0 + n > ix->nlabelled || (n > 0 && !out_host))
+        return fail(MIPS_E_INVALID, "mips_index_read_labels: bad range [%lld, +%lld) of %lld labelled rows", (long long)row0, (long long)n,
+                    ix ? (long long)ix->nlabelled : -1LL);
+    if (n == 0) return MIPS_OK;
+    DeviceGuard g(ix->device);
+    hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st);
+    HIP_TRY(hipMemcpyAsync(out_host, ix->labels + row0, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return MIPS_OK;
 }
 
@@ -509,9 +559,10 @@ static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq,
     return MIPS_OK;
 }
 
-// sel_bits == NULL: the unfiltered search (sel_nbits and sel_bit0 are not looked at)
+// sel_bits == NULL: the unfiltered search (sel_nbits and sel_bit0 are not looked at); q_labels == NULL: no group filter
 static int search_wide_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
-                            int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
+                            int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream,
+                            const int32_t* q_labels = nullptr, int grp_mode = 0) {
     if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
     if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "%s: negative nq or k", who);
     if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "%s: k = %d exceeds MIPS_MAX_K_WIDE = %d", who, k, MIPS_MAX_K_WIDE);
@@ -522,6 +573,12 @@ static int search_wide_impl(const char* who, mips_index_t* ix, const void* q, in
     if (sel_bits && (sel_bit0 < 0 || sel_nbits < 0 || sel_bit0 > sel_nbits || ix->ntotal > sel_nbits - sel_bit0))
         return fail(MIPS_E_INVALID, "%s: the selector's %lld bits from bit %lld on do not cover the index's %lld rows", who, (long long)sel_nbits,
                     (long long)sel_bit0, (long long)ix->ntotal);
+    if (q_labels) {
+        if (grp_mode != MIPS_GRP_EXCLUDE && grp_mode != MIPS_GRP_ONLY) return fail(MIPS_E_INVALID, "%s: grp_mode must be 0 (exclude) or 1 (only), got %d", who, grp_mode);
+        if (ix->nlabelled != ix->ntotal)
+            return fail(MIPS_E_INVALID, "%s: %lld of the index's %lld rows carry a label (mips_index_set_labels)", who, (long long)ix->nlabelled,
+                        (long long)ix->ntotal);
+    }
     if (nq == 0 || k == 0) return MIPS_OK;
     const bool packed = (flags & MIPS_OUT_PACKED) != 0;
     if (packed && !(flags & MIPS_OUT_DEVICE)) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE", who);
@@ -564,6 +621,9 @@ static int search_wide_impl(const char* who, mips_index_t* ix, const void* q, in
         sel.nbits = sel_nbits;
         sel.bit0 = sel_bit0;
         sel.dev = (flags & MIPS_SEL_DEVICE) != 0;
+        sel.qlab = q_labels;
+        sel.qlab_dev = (flags & MIPS_GRP_DEVICE) != 0;
+        sel.grp_only = grp_mode == MIPS_GRP_ONLY ? 1 : 0;
         const int rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, st);
         if (rc) return rc;
     }
@@ -594,7 +654,7 @@ int mips_search_wide_sel(mips_index_t* ix, const void* q, int q_dtype, int64_t n
 
 static int range_search_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
                              float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, const uint8_t* sel_bits,
-                             int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
+                             int64_t sel_nbits, int64_t sel_bit0, void* hip_stream, const int32_t* q_labels = nullptr, int grp_mode = 0) {
     if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
     if (nq < 0 || cap < 0) return fail(MIPS_E_INVALID, "%s: negative nq or cap", who);
     if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED does not apply to a CSR result", who);
@@ -607,6 +667,12 @@ static int range_search_impl(const char* who, mips_index_t* ix, const void* q, i
     if (sel_bits && (sel_bit0 < 0 || sel_nbits < 0 || sel_bit0 > sel_nbits || ix->ntotal > sel_nbits - sel_bit0))
         return fail(MIPS_E_INVALID, "%s: the selector's %lld bits from bit %lld on do not cover the index's %lld rows", who, (long long)sel_nbits,
                     (long long)sel_bit0, (long long)ix->ntotal);
+    if (q_labels) {
+        if (grp_mode != MIPS_GRP_EXCLUDE && grp_mode != MIPS_GRP_ONLY) return fail(MIPS_E_INVALID, "%s: grp_mode must be 0 (exclude) or 1 (only), got %d", who, grp_mode);
+        if (ix->nlabelled != ix->ntotal)
+            return fail(MIPS_E_INVALID, "%s: %lld of the index's %lld rows carry a label (mips_index_set_labels)", who, (long long)ix->nlabelled,
+                        (long long)ix->ntotal);
+    }
     for (int64_t j = 0; j < nq; ++j)
         if (radii[j] != radii[j]) return fail(MIPS_E_INVALID, "%s: radii[%lld] is NaN", who, (long long)j);
     DeviceGuard g(ix->device);
@@ -644,6 +710,9 @@ static int range_search_impl(const char* who, mips_index_t* ix, const void* q, i
         sel.nbits = sel_nbits;
         sel.bit0 = sel_bit0;
         sel.dev = (flags & MIPS_SEL_DEVICE) != 0;
+        sel.qlab = q_labels;
+        sel.qlab_dev = (flags & MIPS_GRP_DEVICE) != 0;
+        sel.grp_only = grp_mode == MIPS_GRP_ONLY ? 1 : 0;
         const int rc = range_search(ix, q, q_dtype, nq, radii, d_lims, d_s, d_i, cap, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, st);
         if (rc) return rc;
     }
@@ -676,6 +745,20 @@ int mips_range_search_sel(mips_index_t* ix, const void* q, int q_dtype, int64_t 
                           int64_t sel_bit0, void* hip_stream) {
     return range_search_impl("mips_range_search_sel", ix, q, q_dtype, nq, radii, out_lims, out_scores, out_idx, cap, idx_offset, flags, sel_bits,
                              sel_nbits, sel_bit0, hip_stream);
+}
+
+int mips_search_wide_grp(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                         int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels,
+                         int grp_mode, void* hip_stream) {
+    return search_wide_impl(q_labels ? "mips_search_wide_grp" : "mips_search_wide_sel", ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags,
+                            sel_bits, sel_nbits, sel_bit0, hip_stream, q_labels, grp_mode);
+}
+
+int mips_range_search_grp(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims, float* out_scores,
+                          int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits,
+                          int64_t sel_bit0, const int32_t* q_labels, int grp_mode, void* hip_stream) {
+    return range_search_impl(q_labels ? "mips_range_search_grp" : "mips_range_search_sel", ix, q, q_dtype, nq, radii, out_lims, out_scores, out_idx, cap,
+                             idx_offset, flags, sel_bits, sel_nbits, sel_bit0, hip_stream, q_labels, grp_mode);
 }
 
 int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64_t nq, int k, int normalize, const int64_t* ignore_device,

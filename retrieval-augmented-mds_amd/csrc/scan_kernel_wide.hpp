@@ -63,11 +63,22 @@ struct WideScanArgs {
     int segcap;           // >= 64 * tiles_per_split
     int* cnt;             // [nqt * TN][2 nsplit]
     const unsigned* sel;  // masked_scan_kernel: staged selector, 4 words per tile (16-byte aligned); wide_scan_kernel: unused
+    const int* rlab;      // grouped_scan_kernel: one label per row, allocated in whole tiles (16-byte aligned)
+    const int* qlab;      // grouped_scan_kernel: [nqt * TN] one label per query (LABEL_NONE: the query is not group-filtered)
+    int grp_only;         // grouped_scan_kernel: 1 = only the rows of the query's group answer, 0 = every row but those
 };
+
+constexpr int LABEL_NONE = -2147483647 - 1; // MIPS_LABEL_NONE
+
+// The group rule of mips_search_wide_grp / mips_range_search_grp: may a row labelled `lab` answer a query labelled `ql`?
+__device__ __forceinline__ bool group_admits(int lab, int ql, int only) { return ql == LABEL_NONE || ((lab == ql) == (only != 0)); }
 
 // SEL: the masked instance (masked_scan_kernel below).  p.sel holds four 32-bit words per tile (select_kernels.hpp): a tile whose
 // words are all zero is never loaded, and a row whose bit is clear never passes the threshold test.
-template <bool SEL>
+// GRP (with SEL): the grouped instance (grouped_scan_kernel).  A lane owns one query, so its label is one register; the labels of
+// the sixteen rows of an accumulator block are four aligned 16-byte loads, made only for a block in which some lane passes the
+// threshold, and a row is appended only if the group rule admits it for the lane's query.
+template <bool SEL, bool GRP = false>
 __device__ __forceinline__ void wide_scan_body(const WideScanArgs& p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
@@ -91,6 +102,8 @@ __device__ __forceinline__ void wide_scan_body(const WideScanArgs& p) {
 
     const int q = qt * TN + wave * 32 + l31;
     const float tau = p.tau[q];
+    int ql = 0;
+    if constexpr (GRP) ql = p.qlab[q];
     const size_t segno = (size_t)q * (2 * p.nsplit) + 2 * split + h;
     wkey_t* myseg = p.seg + segno * p.segcap;
     int cur = 0;
@@ -179,10 +192,21 @@ __device__ __forceinline__ void wide_scan_body(const WideScanArgs& p) {
 #pragma unroll
             for (int r = 1; r < 16; ++r) mx = fmaxf(mx, acc[m][r]);
             if (__ballot(mx > tau) != 0ull) {
+                unsigned adm = 0xffffu; // bit r: row r of the block may answer this lane's query
+                if constexpr (GRP) {
+                    const u32x4* lab4 = reinterpret_cast<const u32x4*>(p.rlab + (int64_t)base + m * 32);
+                    adm = 0u;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const u32x4 lb = lab4[2 * g];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) adm |= group_admits((int)lb[c], ql, p.grp_only) ? 1u << (4 * g + c) : 0u;
+                    }
+                }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float s = acc[m][r];
-                    if (s > tau && cur < p.segcap) {
+                    if (s > tau && (!GRP || ((adm >> r) & 1u) != 0u) && cur < p.segcap) {
                         myseg[cur] = wide_pack(thr_encode(s + 0.0f), base + m * 32 + (r & 3) + 8 * (r >> 2));
                         ++cur;
                     }
@@ -250,6 +274,8 @@ __device__ __forceinline__ void wide_scan_body(const WideScanArgs& p) {
 __global__ __launch_bounds__(SCAN_THREADS, 2) void wide_scan_kernel(WideScanArgs p) { wide_scan_body<false>(p); }
 // the instance of the filtered searches (its name stays outside the census of scan instances, tests/scan_recipes.py)
 __global__ __launch_bounds__(SCAN_THREADS, 2) void masked_scan_kernel(WideScanArgs p) { wide_scan_body<true>(p); }
+// the instance of the grouped searches (outside the census too): always reads staged selector words, all ones without a bitmap
+__global__ __launch_bounds__(SCAN_THREADS, 2) void grouped_scan_kernel(WideScanArgs p) { wide_scan_body<true, true>(p); }
 
 // ------------------------------------------------------------------------------------------------------------- select
 // descending bitonic sort of buf[0 .. n) in LDS by the whole workgroup (n <= WIDE_BUF; pads with 0 = "no entry")
@@ -402,7 +428,10 @@ struct WideRescoreArgs {
 
 // SEL: a filtered search.  The rows that can be results are the nsel selected ones, so the two uses of ntotal in the certificate
 // read that count instead.
-template <typename EL, bool L2, bool SEL = false>
+// GRP: a grouped search.  The rows admitted for a query are not counted anywhere.  A pool short of k' entries IS the query's whole
+// admitted set (wide_select_kernel keeps tau_f at -inf until a pool holds k' entries, and under -inf the scan appends every
+// admitted row), so such a query is certified outright; a full pool takes the bound check whatever lies outside it.
+template <typename EL, bool L2, bool SEL = false, bool GRP = false>
 __global__ __launch_bounds__(WIDE_THREADS) void wide_rescore_kernel(WideRescoreArgs a) {
     __shared__ double yd[1024];
     __shared__ double dd[WIDE_POOL];
@@ -469,9 +498,9 @@ __global__ __launch_bounds__(WIDE_THREADS) void wide_rescore_kernel(WideRescoreA
         const int64_t nrows = SEL ? (int64_t)*a.nsel : a.ntotal;
         const int64_t need = nrows < (int64_t)a.kp ? nrows : (int64_t)a.kp;
         bool fl = false;
-        if ((int64_t)n < need) {
+        if (GRP ? false : (int64_t)n < need) {
             fl = true;
-        } else if (nrows > (int64_t)n) {
+        } else if (GRP ? n >= a.kp : nrows > (int64_t)n) {
             const double B = (double)thr_decode(minhi_s);
             const double qn = sqrt(qq), xm = sqrt(*a.xmax2);
             double e = a.err_c * qn * xm;
@@ -517,6 +546,9 @@ struct WideExactArgs {
     int64_t* out_i;
     int64_t* out_packed;
     const unsigned* sel; // SEL: staged selector words (bit r & 31 of word r >> 5 = local row r), zero past ntotal
+    const int* rlab;     // GRP: one label per row
+    const int* qlab;     // GRP: one label per query of the slice (indexed like y)
+    int grp_only;        // GRP: 1 = only mode, 0 = exclude mode
 };
 
 // start of a round: empty pools; a row must reach the k-th result of the first pass to matter
@@ -531,7 +563,9 @@ __global__ void wide_exact_init_kernel(WideExactArgs a) {
 
 // SEL: a filtered search.  An unselected row is never appended (the settlement must not bring back what the scan left out), and a
 // wave's 64 rows are not scored at all when none of them is selected.
-template <typename EL, bool L2, bool SEL = false>
+// GRP (with SEL): a grouped search.  Each of the RESOLVE_QB queries of a pass has its own label, so the group rule is tested per
+// (query, row) next to the threshold; the wave-level skip stays on the bitmap alone.
+template <typename EL, bool L2, bool SEL = false, bool GRP = false>
 __global__ __launch_bounds__(64 * RESOLVE_WAVES) void wide_exact_kernel(WideExactArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int n = *a.n_dev;
@@ -558,11 +592,14 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void wide_exact_kernel(WideExac
         __syncthreads();
         wkey_t tau[RESOLVE_QB];
         double qn[RESOLVE_QB];
+        int ql[RESOLVE_QB];
 #pragma unroll
         for (int j = 0; j < RESOLVE_QB; ++j) {
             const bool on = j0 + j < jend;
             tau[j] = on ? a.tau_c[j0 + j - a.slot0] : ~0ull;
             qn[j] = on && L2 ? a.qq[a.ids[j0 + j]] : 0.0;
+            ql[j] = LABEL_NONE;
+            if constexpr (GRP) ql[j] = on ? a.qlab[a.ids[j0 + j]] : LABEL_NONE;
         }
         for (int64_t r0 = a.r0 + ((int64_t)blockIdx.x * RESOLVE_WAVES + wave) * 64; r0 < a.r1; r0 += (int64_t)gridDim.x * 64 * RESOLVE_WAVES) {
             const int64_t row = r0 + lane;
@@ -574,11 +611,13 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void wide_exact_kernel(WideExac
             double acc[RESOLVE_QB];
             exact_dots<EL>(rows, a.ld, a.ntotal, r0, lane, tile, yd, acc);
             if (row < a.r1 && on) {
+                int lab = 0;
+                if constexpr (GRP) lab = a.rlab[row];
 #pragma unroll
                 for (int j = 0; j < RESOLVE_QB; ++j) {
                     const float outv = L2 ? (float)(qn[j] + a.phi - 2.0 * acc[j]) : (float)acc[j];
                     const wkey_t c = wide_pack(wide_enc<L2>(outv), (int)row);
-                    if (c > tau[j]) {
+                    if ((!GRP || group_admits(lab, ql[j], a.grp_only)) && c > tau[j]) {
                         const int slot = j0 + j - a.slot0;
                         const int pos = atomicAdd(&a.cnt[slot], 1);
                         if (pos < a.segcap) a.seg[(size_t)slot * a.segcap + pos] = c;

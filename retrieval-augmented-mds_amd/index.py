@@ -29,14 +29,49 @@ def _stream_handle(device: int) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def as_labels(a, what: str, device: int | None = None):
+    """An int array (NumPy / sequence -> host, torch CUDA tensor -> device) as contiguous 1-d int32 labels; values outside
+    int32 raise ValueError.  A CUDA tensor that is not int32 already is range-checked on the host, which synchronises.
+    -> (np.ndarray | CUDA tensor, is_device)"""
+    import torch
+
+    lo, hi = -(1 << 31), (1 << 31) - 1
+    if isinstance(a, torch.Tensor):
+        if a.dtype.is_floating_point or a.dtype.is_complex or a.dtype == torch.bool:
+            raise ValueError(f"{what}: expected integers, got {a.dtype}")
+        a = a.reshape(-1)
+        if a.is_cuda:
+            if a.dtype != torch.int32:
+                if a.numel() and (int(a.min()) < lo or int(a.max()) > hi):
+                    raise ValueError(f"{what}: values outside int32")
+                a = a.to(torch.int32)
+            if device is not None and a.device.index != device:
+                a = a.to(f"cuda:{device}")
+            return a.contiguous(), True
+        a = a.numpy()
+    a = np.asarray(a).reshape(-1)
+    if a.size == 0:
+        return np.zeros(0, np.int32), False
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"{what}: expected integers, got {a.dtype}")
+    if a.dtype != np.int32 and (int(a.min()) < lo or int(a.max()) > hi):
+        raise ValueError(f"{what}: values outside int32")
+    return np.ascontiguousarray(a, dtype=np.int32), False
+
+
+_GROUP_MODES = {"exclude": _lib.GRP_EXCLUDE, "only": _lib.GRP_ONLY}
+
+
 def route_search(index, q, k: int, **kwargs):
     """index.search(q, k), or index.search_wide(q, k) when k exceeds MAX_K and the index has a wide search (MipsIndex and
     ShardedMipsIndex do; foreign duck-typed indexes keep their own search and its limits).  A call carrying selector= (a
-    filtered search) goes to search_wide whatever k is: search() itself has no selector."""
-    if "selector" in kwargs:
-        if kwargs["selector"] is not None:
-            return index.search_wide(q, int(k), **kwargs)
+    filtered search) or groups= (a grouped one) goes to search_wide whatever k is: search() itself has neither."""
+    if "groups" in kwargs and kwargs["groups"] is None:
+        kwargs = {key: v for key, v in kwargs.items() if key not in ("groups", "group_mode")}
+    if "selector" in kwargs and kwargs["selector"] is None:
         kwargs = {key: v for key, v in kwargs.items() if key != "selector"}
+    if "selector" in kwargs or "groups" in kwargs:
+        return index.search_wide(q, int(k), **kwargs)
     if int(k) > _lib.MAX_K and hasattr(index, "search_wide"):
         return index.search_wide(q, int(k), **kwargs)
     return index.search(q, k, **kwargs)
@@ -60,6 +95,7 @@ class MipsIndex:
         self.dtype = dtype
         self.nprobe = 1  # accepted for drop-in compatibility (mips.py:342-345); exact search ignores it
         self._mutex = threading.Lock()
+        self._nlabelled = 0  # rows [0, _nlabelled) carry a group label (set_labels)
 
     # ------------------------------------------------------------------ faiss-like attributes
     @property
@@ -143,6 +179,49 @@ class MipsIndex:
 
     def reset(self) -> None:
         _lib.check(self._lib.mips_index_reset(self._h), "mips_index_reset")
+        self._nlabelled = 0
+
+    def set_labels(self, labels, row0: int = 0) -> None:
+        """One int32 group label per row for rows [row0, row0 + len(labels)) (NumPy or torch int array, host or CUDA): what
+        groups= of search_wide / range_search tests.  The labelled rows are a prefix of the index -- row0 may not lie behind
+        the rows labelled so far -- so a build that adds in batches labels as it goes; labelled rows may be rewritten.  The
+        labels survive reserve() and growth; reset() clears them."""
+        lab, is_dev = as_labels(labels, "set_labels", self.device)
+        n, row0 = int(lab.shape[0]), int(row0)
+        if row0 < 0 or row0 + n > self.ntotal:
+            raise ValueError(f"set_labels: rows [{row0}, {row0 + n}) of an index of {self.ntotal}")
+        if row0 > self._nlabelled:
+            raise ValueError(f"set_labels: row0 = {row0} leaves a gap behind the {self._nlabelled} labelled rows")
+        with self._mutex:
+            _lib.check(self._lib.mips_index_set_labels(self._h, lab.data_ptr() if is_dev else lab.ctypes.data, row0, n, int(is_dev),
+                                                       _stream_handle(self.device)), "mips_index_set_labels")
+            self._nlabelled = max(self._nlabelled, row0 + n)
+        del lab
+
+    def labels(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        """The labels of the labelled rows [row0, row0 + n) as np.int32 (n = None: up to the last labelled row)."""
+        n = self._nlabelled - int(row0) if n is None else int(n)
+        if row0 < 0 or n < 0 or row0 + n > self._nlabelled:
+            raise ValueError(f"labels: rows [{row0}, {row0 + n}) of {self._nlabelled} labelled rows")
+        out = np.empty(n, dtype=np.int32)
+        with self._mutex:
+            _lib.check(self._lib.mips_index_read_labels(self._h, int(row0), n, out.ctypes.data, _stream_handle(self.device)),
+                       "mips_index_read_labels")
+        return out
+
+    def _grp_args(self, groups, group_mode, nq: int, what: str):
+        """groups (None | int array [nq]: NumPy -> host, CUDA tensor -> device) -> (pointer, mode, flag, keepalive) of the
+        *_grp entry points."""
+        if groups is None:
+            return None, 0, 0, None
+        if group_mode not in _GROUP_MODES:
+            raise ValueError(f"{what}: group_mode must be 'exclude' or 'only', got {group_mode!r}")
+        if self._nlabelled != self.ntotal:
+            raise ValueError(f"{what}: groups= needs a label on every row; {self._nlabelled} of {self.ntotal} rows carry one (set_labels)")
+        g, is_dev = as_labels(groups, what + ": groups", self.device)
+        if g.shape[0] != nq:
+            raise ValueError(f"{what}: expected {nq} group labels, got {g.shape[0]}")
+        return (g.data_ptr() if is_dev else g.ctypes.data), _GROUP_MODES[group_mode], (_lib.GRP_DEVICE if is_dev else 0), g
 
     def phi(self) -> float:
         out = ctypes.c_double()
@@ -245,19 +324,24 @@ class MipsIndex:
             raise ValueError(f"{what}: the selector has {nbits} bits; rows {sel_bit0} .. {sel_bit0 + self.ntotal} of it are needed")
         return ptr, nbits, flag, keep
 
-    def search_wide(self, x, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, sel_bit0: int = 0):
+    def search_wide(self, x, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, sel_bit0: int = 0, groups=None,
+                    group_mode: str = "exclude"):
         """search() for k up to MAX_K_WIDE = 1024 (mips_search_wide: threshold scan, streaming select, exact re-score; every
         query certified or settled exactly in the same call).  bf16 and f32 indexes of at most 1024 columns.  NumPy in ->
         NumPy out; torch CUDA tensor in -> torch CUDA tensors out, stream-ordered, no synchronisation.
         selector (a Selector, a bool mask or a NumPy uint8 bitmap; one for all queries): only the selected rows can be results
         -- what the search returns on an index from which the others were deleted, row numbers, phi and maximal norm kept;
-        fewer than k selected rows leave the -1 / -+inf padding.  Bit sel_bit0 + i of the selector decides local row i."""
+        fewer than k selected rows leave the -1 / -+inf padding.  Bit sel_bit0 + i of the selector decides local row i.
+        groups (an int array [nq], NumPy -> host, CUDA tensor -> device) with group_mode: one label per query, tested against
+        the row labels of set_labels -- "exclude": only rows of ANOTHER label answer the query, "only": only rows of ITS label;
+        a query labelled LABEL_NONE is not filtered.  Applies on top of the selector, with the same definition per query."""
         import torch
 
         k = int(k)
         self._check_wide(k)
         sel_ptr, sel_nbits, sel_flag, sel_keep = self._sel_args(selector, sel_bit0, "search_wide")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self._grp_args(groups, group_mode, nq, "search_wide")
         stream = _stream_handle(self.device)
         if is_dev:
             dev = f"cuda:{self.device}"
@@ -273,13 +357,17 @@ class MipsIndex:
         if force_ip:
             flags |= _lib.FORCE_IP
         with self._mutex:
-            if selector is None:
+            if groups is not None:
+                _lib.check(self._lib.mips_search_wide_grp(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags | sel_flag | grp_flag,
+                                                          sel_ptr, sel_nbits, int(sel_bit0), grp_ptr, grp_mode, stream),
+                           "mips_search_wide_grp")
+            elif selector is None:
                 _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags, stream),
                            "mips_search_wide")
             else:
                 _lib.check(self._lib.mips_search_wide_sel(self._h, ptr, code, nq, k, ds, di, int(idx_offset), flags | sel_flag,
                                                           sel_ptr, sel_nbits, int(sel_bit0), stream), "mips_search_wide_sel")
-        del keep, sel_keep
+        del keep, sel_keep, grp_keep
         return D, I
 
     def _check_wide(self, k: int) -> None:
@@ -312,16 +400,19 @@ class MipsIndex:
             raise ValueError("range_search: a radius is NaN")
         return r
 
-    def range_search_into(self, x, radius, lims, D, I, idx_offset: int = 0, force_ip: bool = False, selector=None) -> None:
+    def range_search_into(self, x, radius, lims, D, I, idx_offset: int = 0, force_ip: bool = False, selector=None, groups=None,
+                          group_mode: str = "exclude") -> None:
         """The non-synchronising form of range_search: the caller allocates the CUDA tensors lims (int64 [nq + 1]), D (float32
         [cap]) and I (int64 [cap]); everything is enqueued on the current stream.  lims always receives the true counts; when
         lims[-1] > cap the contents of D and I are unspecified and the call is to be repeated with larger tensors.  cap = 0
-        (empty D and I) is a counting call.  `radius` is host data (a scalar or nq values).  selector: as in search_wide."""
+        (empty D and I) is a counting call.  `radius` is host data (a scalar or nq values).  selector, groups and
+        group_mode: as in search_wide."""
         import torch
 
         self._check_range()
         sel_ptr, sel_nbits, sel_flag, sel_keep = self._sel_args(selector, 0, "range_search")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self._grp_args(groups, group_mode, nq, "range_search")
         r = self._radii(radius, nq)
         dev = torch.device("cuda", self.device)
         for t, dt, what in ((lims, torch.int64, "lims"), (D, torch.float32, "D"), (I, torch.int64, "I")):
@@ -332,7 +423,12 @@ class MipsIndex:
         cap = int(D.shape[0])
         flags = _lib.OUT_DEVICE | (_lib.Q_DEVICE if is_dev else 0) | (_lib.FORCE_IP if force_ip else 0)
         with self._mutex:
-            if selector is None:
+            if groups is not None:
+                _lib.check(self._lib.mips_range_search_grp(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
+                                                           D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
+                                                           int(idx_offset), flags | sel_flag | grp_flag, sel_ptr, sel_nbits, 0, grp_ptr,
+                                                           grp_mode, _stream_handle(self.device)), "mips_range_search_grp")
+            elif selector is None:
                 _lib.check(self._lib.mips_range_search(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
                                                        D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
                                                        int(idx_offset), flags, _stream_handle(self.device)), "mips_range_search")
@@ -341,16 +437,18 @@ class MipsIndex:
                                                            D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
                                                            int(idx_offset), flags | sel_flag, sel_ptr, sel_nbits, 0,
                                                            _stream_handle(self.device)), "mips_range_search_sel")
-        del keep, sel_keep
+        del keep, sel_keep, grp_keep
 
-    def range_search(self, x, radius, idx_offset: int = 0, force_ip: bool = False, selector=None):
+    def range_search(self, x, radius, idx_offset: int = 0, force_ip: bool = False, selector=None, groups=None,
+                     group_mode: str = "exclude"):
         """faiss Index.range_search(x, radius) -> (lims, D, I): every stored row whose canonical score is strictly above the
         radius (inner product; L2: whose distance |q|^2 + phi - 2 q.x is strictly below it).  `radius` is a scalar or nq
         values.  The hits of query j are D / I [lims[j] : lims[j + 1]], in ascending row order; lims is int64 [nq + 1].
         NumPy in -> NumPy out; torch CUDA tensor in -> torch CUDA tensors out.  The result's size is not known beforehand: a
         first call runs with a guessed capacity, lims[-1] is READ ON THE HOST -- THIS SYNCHRONISES the stream -- and one repeat
         with the exact size follows if the guess was too small (range_search_into is the form that never synchronises).
-        bf16 and f32 indexes of at most 1024 columns.  selector (as in search_wide): only selected rows can be hits."""
+        bf16 and f32 indexes of at most 1024 columns.  selector (as in search_wide): only selected rows can be hits; groups
+        and group_mode (as in search_wide): only rows the group rule admits for the query."""
         import torch
 
         from .selector import Selector
@@ -368,7 +466,8 @@ class MipsIndex:
         while True:
             D = torch.empty(cap, dtype=torch.float32, device=dev)
             I = torch.empty(cap, dtype=torch.int64, device=dev)
-            self.range_search_into(keep, r, lims, D, I, idx_offset=idx_offset, force_ip=force_ip, selector=selector)
+            self.range_search_into(keep, r, lims, D, I, idx_offset=idx_offset, force_ip=force_ip, selector=selector, groups=groups,
+                                   group_mode=group_mode)
             total = int(lims[-1].item())   # the synchronisation
             if total <= cap:
                 break
@@ -378,10 +477,12 @@ class MipsIndex:
             return lims, D.clone() if total < cap else D, I.clone() if total < cap else I
         return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
 
-    def search_wide_packed(self, x, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, sel_bit0: int = 0):
+    def search_wide_packed(self, x, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, sel_bit0: int = 0, groups=None,
+                           group_mode: str = "exclude"):
         """Device-only search_wide returning the all-gather payload: CUDA int64 [nq, k, 2] = {float32 score bits,
         index + idx_offset}, row for row what search_wide returns (padding included).  selector / sel_bit0 as in search_wide:
-        a row shard passes the global selector and its first global row."""
+        a row shard passes the global selector and its first global row.  groups / group_mode as in search_wide (the row labels
+        are the shard's own)."""
         import torch
 
         k = int(k)
@@ -390,17 +491,22 @@ class MipsIndex:
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         if not is_dev:
             raise ValueError("search_wide_packed needs a CUDA tensor")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self._grp_args(groups, group_mode, nq, "search_wide_packed")
         out = torch.empty((nq, k, 2), dtype=torch.int64, device=f"cuda:{self.device}")
         flags = _lib.Q_DEVICE | _lib.OUT_DEVICE | _lib.OUT_PACKED | (_lib.FORCE_IP if force_ip else 0)
         with self._mutex:
-            if selector is None:
+            if groups is not None:
+                _lib.check(self._lib.mips_search_wide_grp(self._h, ptr, code, nq, k, None, out.data_ptr(), int(idx_offset),
+                                                          flags | sel_flag | grp_flag, sel_ptr, sel_nbits, int(sel_bit0), grp_ptr, grp_mode,
+                                                          _stream_handle(self.device)), "mips_search_wide_grp")
+            elif selector is None:
                 _lib.check(self._lib.mips_search_wide(self._h, ptr, code, nq, k, None, out.data_ptr(), int(idx_offset), flags,
                                                       _stream_handle(self.device)), "mips_search_wide")
             else:
                 _lib.check(self._lib.mips_search_wide_sel(self._h, ptr, code, nq, k, None, out.data_ptr(), int(idx_offset),
                                                           flags | sel_flag, sel_ptr, sel_nbits, int(sel_bit0),
                                                           _stream_handle(self.device)), "mips_search_wide_sel")
-        del keep, sel_keep
+        del keep, sel_keep, grp_keep
         return out
 
     def search_fused(self, x, k: int, normalize: bool = False, ignore=None, idx_offset: int = 0):
@@ -508,6 +614,7 @@ class MipsIndex:
     # Own format (the on-disk format is free, the call surface is kept):
     #   <path>/meta.json   {"format":1,"d":..,"ntotal":..,"metric":..,"dtype":"bf16", ...}
     #   <path>/rows.bf16   raw little-endian bf16 bit patterns [ntotal, d]   (rows.e4m3: e4m3 bytes)
+    #   <path>/labels.i32  little-endian int32 [ntotal], only with "labels": true in meta.json (a fully labelled index)
     def save(self, path: str, extra: dict | None = None, chunk_rows: int = 1 << 16) -> None:
         """Replaces Dataset.save_faiss_index (sotasum/mips.py:536)."""
         os.makedirs(path, exist_ok=True)
@@ -520,6 +627,10 @@ class MipsIndex:
             # phi of the WHOLE file: a rank that loads one row range of it must not fall back to its own rows' maximum
             # (L2 distances of different shards would not be comparable)
             meta["phi"] = self.phi()
+        if n > 0 and self._nlabelled == n:
+            with open(os.path.join(path, "labels.i32"), "wb") as f:
+                f.write(self.labels().astype("<i4").tobytes())
+            meta["labels"] = True
         if extra:
             meta.update({k: v for k, v in extra.items() if v is not None or k not in meta})
         with open(os.path.join(path, "meta.json"), "w") as f:
@@ -545,6 +656,10 @@ class MipsIndex:
             for r0 in range(lo, hi, chunk_rows):
                 ix.add(np.asarray(mm[r0:min(hi, r0 + chunk_rows)]))
             del mm
+            if meta.get("labels"):
+                lab = np.memmap(os.path.join(path, "labels.i32"), dtype="<i4", mode="r", shape=(n,))
+                ix.set_labels(np.asarray(lab[lo:hi]))
+                del lab
         if row_range is not None and meta["metric"] == _lib.METRIC_L2 and meta.get("phi") is not None:
             ix.set_phi(float(meta["phi"]))  # the file's phi, not this row range's
         ix.meta = meta

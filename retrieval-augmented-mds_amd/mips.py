@@ -38,6 +38,7 @@ from .index import MipsIndex, l2_normalize_, route_search, rows_max_sumsq, rows_
 
 METRIC_INNER_PRODUCT = _lib.METRIC_IP
 METRIC_L2 = _lib.METRIC_L2
+LABEL_NONE = _lib.LABEL_NONE
 
 
 @dataclass
@@ -209,6 +210,7 @@ class KnowledgeBase:
         self.columns = columns
         self._indexes = {index_name: _IndexHolder(index)} if index is not None else {}
         self._index_columns = {}   # index name -> the column add_faiss_index built it from
+        self._groups = {}          # index name -> (column, its sorted distinct values): set_groups
 
     def __len__(self):
         return len(next(iter(self.columns.values()))) if self.columns else 0
@@ -227,10 +229,37 @@ class KnowledgeBase:
     def add_index(self, name: str, index: MipsIndex):
         self._indexes[name] = _IndexHolder(index)
         self._index_columns.pop(name, None)
+        self._groups.pop(name, None)
 
     def drop_index(self, name: str):
         self._indexes.pop(name, None)
         self._index_columns.pop(name, None)
+        self._groups.pop(name, None)
+
+    def set_groups(self, index_name: str, column: str):
+        """Makes `column` (any values np.unique orders: article ids, strings) the GROUP of every row of the index: the distinct
+        values become the dense codes 0 .. U - 1, the index is labelled with them (MipsIndex.set_labels; a row-sharded index
+        keeps its own rows' labels) and the mapping is kept for get_nearest_examples_batch(groups=...)."""
+        uniq, inv = np.unique(np.asarray(self.columns[column]), return_inverse=True)
+        index = self.get_index(index_name).faiss_index
+        codes = np.ascontiguousarray(inv.reshape(-1), dtype=np.int32)
+        (index.set_labels_global if hasattr(index, "set_labels_global") else index.set_labels)(codes)
+        self._groups[index_name] = (column, uniq)
+        return self
+
+    def group_codes(self, index_name: str, values, group_mode: str = "exclude") -> np.ndarray:
+        """Per-query VALUES of the group column -> the int32 labels a grouped search takes.  A value the column does not contain
+        becomes LABEL_NONE in exclude mode (there is nothing to exclude) and the code U, which no row has, in only mode
+        (nothing can answer)."""
+        if group_mode not in ("exclude", "only"):
+            raise ValueError(f"group_mode must be 'exclude' or 'only', got {group_mode!r}")
+        if index_name not in self._groups:
+            raise ValueError(f"index {index_name!r} has no groups (call set_groups first)")
+        uniq = self._groups[index_name][1]
+        vals = np.asarray(values).reshape(-1)
+        pos = np.minimum(np.searchsorted(uniq, vals), max(len(uniq) - 1, 0))
+        found = uniq[pos] == vals if len(uniq) else np.zeros(len(vals), bool)
+        return np.where(found, pos, LABEL_NONE if group_mode == "exclude" else len(uniq)).astype(np.int32)
 
     def add_faiss_index(self, column: str, index_name: str = None, device: int = None, string_factory: str = None,
                         metric_type: int = None, custom_index=None, batch_size: int = 1000, train_size: int = None,
@@ -313,15 +342,20 @@ class KnowledgeBase:
         order = np.lexsort((j, i))
         return i[order], j[order], s[order]
 
-    def get_nearest_examples_batch(self, index_name: str, queries, k: int = 10, selector=None):
+    def get_nearest_examples_batch(self, index_name: str, queries, k: int = 10, selector=None, groups=None, group_mode: str = "exclude"):
         """HF Dataset.get_nearest_examples_batch as used at retriever_lightning.py:317-321: returns (scores
         per query, examples per query as dict of columns); ids < 0 are dropped like datasets/search.py does.
         L2 indexes take the reference's augmented queries ([B, d + 1], zero last column) as they come.
         selector (ram.Selector, bool mask or NumPy bitmap over the rows): only selected rows are retrieved -- one partition of
-        a knowledge base, an `aid` group, everything but a cluster of near duplicates."""
+        a knowledge base, an `aid` group, everything but a cluster of near duplicates.
+        groups (per-query VALUES of the column given to set_groups) with group_mode: "exclude" keeps the rows of the query's
+        own group out of its result (leak-free retrieval, hard negatives), "only" searches inside that group."""
         index = self.get_index(index_name).faiss_index
         q = _strip_augmentation_column(index, np.asarray(queries, dtype=np.float32))
-        s, i = route_search(index, np.ascontiguousarray(q), k, **({} if selector is None else {"selector": selector}))
+        kw = {} if selector is None else {"selector": selector}
+        if groups is not None:
+            kw.update(groups=self.group_codes(index_name, groups, group_mode), group_mode=group_mode)
+        s, i = route_search(index, np.ascontiguousarray(q), k, **kw)
         scores, examples = [], []
         for row_s, row_i in zip(s, i):
             keep = row_i >= 0
@@ -613,12 +647,20 @@ class Mips:
             raise RuntimeError("Mips: no index (call build_index() or load() first)")
         return self.embeddings.get_index(self.index_name).faiss_index
 
-    def search(self, queries: np.ndarray, ignore_indexes: list = None, k: int = 10):
+    def search(self, queries: np.ndarray, ignore_indexes: list = None, k: int = 10, ignore_groups: list = None):
         """mips.py:382-400: k (or k+1 when filtering) nearest rows; with ignore_indexes the hit
-        equal to ignore_indexes[j] is dropped per query and the rest cut to k (lists of lists)."""
+        equal to ignore_indexes[j] is dropped per query and the rest cut to k (lists of lists).
+        ignore_groups (per-query values of index_column, e.g. the queries' `aid`): no row of that group is retrieved -- what
+        the reference's one-id filter cannot do, a group has no bounded size.  The groups are set on first use; both filters
+        combine."""
         index = self._index()
         q = _strip_augmentation_column(index, np.asarray(queries))  # the zero column of augment_xq
-        scores, indices = route_search(index, q, k + 1 if ignore_indexes is not None else k)
+        kw = {}
+        if ignore_groups is not None:
+            if self.index_name not in self.embeddings._groups:
+                self.embeddings.set_groups(self.index_name, self.index_column)
+            kw = {"groups": self.embeddings.group_codes(self.index_name, ignore_groups, "exclude"), "group_mode": "exclude"}
+        scores, indices = route_search(index, q, k + 1 if ignore_indexes is not None else k, **kw)
         if ignore_indexes is not None:
             out_s, out_i = [], []
             for j in range(len(indices)):
@@ -673,7 +715,7 @@ class Mips:
 
     # ------------------------------------------------------------------ forward (mips.py:402-463)
     def forward(self, queries: np.ndarray, aid: list = None, aid_counts=None, target_str: list = None,
-                input_str: list = None, ignore_indexes: list = None, k: int = 10) -> MipsModelOutput:
+                input_str: list = None, ignore_indexes: list = None, k: int = 10, ignore_own_group: bool = False) -> MipsModelOutput:
         a = self.args
         indices = None
         if a.memory_forcing == "target_only" and a.multi_x_science_dataset_mode == "original":
@@ -683,7 +725,12 @@ class Mips:
             examples = [target_str]
         else:
             queries = self._prepare_query(query=queries)
-            scores, indices = self.search(queries=queries, ignore_indexes=ignore_indexes, k=k)
+            if ignore_own_group:  # leak-free retrieval: no row of the query's own `aid` group
+                if aid is None:
+                    raise ValueError("forward(ignore_own_group=True) needs aid")
+                scores, indices = self.search(queries=queries, ignore_indexes=ignore_indexes, k=k, ignore_groups=aid)
+            else:
+                scores, indices = self.search(queries=queries, ignore_indexes=ignore_indexes, k=k)
             examples = [self.embeddings[[i for i in row if i >= 0]][self.text_column] for row in indices]
 
             if (a.memory_forcing == "target_in" and a.multi_x_science_dataset_mode == "original"

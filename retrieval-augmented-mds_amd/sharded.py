@@ -102,6 +102,13 @@ class ShardedMipsIndex:
             self.local.add_synthetic(hi - lo, row0=lo, seed=seed, kind=kind)
         self._sync_phi()
 
+    def set_labels_global(self, labels) -> None:
+        """Every rank sees the full [N] int array of row labels (MipsIndex.set_labels) and keeps those of its own rows."""
+        if len(labels) != self.ntotal_global:
+            raise ValueError(f"set_labels_global: {len(labels)} labels for {self.ntotal_global} rows")
+        if self.local is not None and self.hi > self.lo:
+            self.local.set_labels(labels[self.lo:self.hi])
+
     def _sync_phi(self) -> None:
         """L2 mode: phi = max_i |x_i|^2 must be the GLOBAL maximum (mips.py:316-324 computes it over the
         whole knowledge base); one scalar all-reduce at build time, not on the search path."""
@@ -288,15 +295,16 @@ class ShardedMipsIndex:
         return ShardedMipsIndex._Pending(out, done, (packed, gathered, q), self.local)
 
     # ------------------------------------------------------------------ search
-    def search(self, q, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None):
+    def search(self, q, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, groups=None, group_mode: str = "exclude"):
         """Replicated queries in, global top-k out (same on every rank).  force_ip: rank by inner product on an
         L2 index (Mips.np_search); idx_offset exists for signature compatibility with MipsIndex.search and must
-        be 0 (global row numbers are the shard offsets' business).  selector: a filtered search, served by search_wide."""
+        be 0 (global row numbers are the shard offsets' business).  selector / groups: a filtered or grouped search, served
+        by search_wide."""
         import torch
         import torch.distributed as dist
 
-        if selector is not None:
-            return self.search_wide(q, k, idx_offset=idx_offset, force_ip=force_ip, selector=selector)
+        if selector is not None or groups is not None:
+            return self.search_wide(q, k, idx_offset=idx_offset, force_ip=force_ip, selector=selector, groups=groups, group_mode=group_mode)
         if idx_offset:
             raise ValueError("ShardedMipsIndex.search returns global row numbers; idx_offset must be 0")
         if force_ip:
@@ -319,14 +327,16 @@ class ShardedMipsIndex:
         s, i = self._local_search(q, k, self.lo)
         return self._exchange(s, i, k, self.metric_type)
 
-    def search_wide(self, q, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None):
+    def search_wide(self, q, k: int, idx_offset: int = 0, force_ip: bool = False, selector=None, groups=None, group_mode: str = "exclude"):
         """search() for k up to MAX_K_WIDE = 1024 (route_search sends k > MAX_K here): every shard runs MipsIndex.search_wide,
         then the same ONE all-gather, then the merge for sorted lists (mips_merge_topk_sorted_packed: the counting merge of
         search() is quadratic in world * k).  bf16 and f32 shards of at most 1024 columns; idx_offset must be 0; force_ip as in
         search().  Every query is certified or settled on its shard, so margin_stats() reports unresolved = 0.  The payload is
         nq * k * 16 bytes per rank -- bandwidth- rather than latency-sized -- and the gathered buffer `world` times that.
         selector: a GLOBAL selector (one bit per global row, the same on every rank; Selector, bool mask or NumPy bitmap); each
-        shard reads its own rows' bits from bit `lo` on, the exchange and the merge are those of the unfiltered search."""
+        shard reads its own rows' bits from bit `lo` on, the exchange and the merge are those of the unfiltered search.
+        groups / group_mode: one label per query, replicated like the queries, tested by every shard against the labels of its
+        own rows (set_labels_global); exchange and merge untouched."""
         import torch
         import torch.distributed as dist
 
@@ -339,6 +349,8 @@ class ShardedMipsIndex:
             if nbits < self.ntotal_global:
                 raise ValueError(f"search_wide: the selector has {nbits} bits, the sharded index {self.ntotal_global} rows")
             sel_kw = {"selector": selector, "sel_bit0": self.lo}
+        if groups is not None:
+            sel_kw.update(groups=groups, group_mode=group_mode)
 
         if idx_offset:
             raise ValueError("ShardedMipsIndex.search_wide returns global row numbers; idx_offset must be 0")
