@@ -333,7 +333,11 @@ int mips_merge_topk_sorted_packed(const int64_t* gathered, int64_t nq, int parts
 
 /* The ignore filter of Mips.search (sotasum/mips.py:388-398) on the device: from k_fetched (= k + 1)
  * hits per query drop every hit whose id equals ignore[q] and keep the first k.  All DEVICE buffers:
- * scores/idx [nq, k_fetched], ignore [nq] int64, out_s/out_i [nq, k]. */
+ * scores/idx [nq, k_fetched], ignore [nq] int64, out_s/out_i [nq, k]; k_fetched >= k.
+ * Every one of the k output slots is written.  When fewer than k hits survive (k_fetched == k with the ignored id
+ * among the hits, the ignored id present more than once, or ignore[q] == -1 on a row that ends in -1 padding), the
+ * slots behind the last survivor get id -1 and score -INFINITY.  The function has no metric argument, so the padding
+ * score is -INFINITY for L2 distances as well: a caller whose lists can run short tells padding by the id. */
 int mips_filter_ignore(const float* scores, const int64_t* idx, const int64_t* ignore, int64_t nq,
                        int k_fetched, int k, float* out_s, int64_t* out_i, int device, void* hip_stream);
 

@@ -10,7 +10,7 @@ namespace mips {
 
 __device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
     uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0; // NaN stays NaN
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)(0x7fc0u | ((u >> 16) & 0x8000u)); // NaN stays NaN, sign kept
     return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t b) { return __uint_as_float(b << 16); }
@@ -894,6 +894,12 @@ __global__ void filter_ignore_kernel(const float* s, const int64_t* id, const in
             out_i[q * k + w] = v;
             ++w;
         }
+    }
+    // fewer than k survivors (k_fetched == k with the banned id present, the banned id twice, or -1 banned on a padded
+    // row): the remaining slots are padding, never whatever the output buffer held before
+    for (; w < k; ++w) {
+        out_s[q * k + w] = -INFINITY;
+        out_i[q * k + w] = -1;
     }
 }
 
