@@ -535,6 +535,14 @@ __global__ __launch_bounds__(64) void merge_select_kernel(MergeArgs p, int* cand
     merge_select_body<KL>(p, cand, (int)blockIdx.x, (int)threadIdx.x);
 }
 
+// Is the float32 key of a row whose inner product is at most `ub` strictly worse than the key of the k-th result (inner
+// product tk)?  The keys are what rank_flag_write orders by: (float) dot, or the distance (float)(|q|^2 + phi - 2 dot).
+template <bool L2>
+__device__ __forceinline__ bool margin_key_worse(double ub, double tk, double qq, double phi) {
+    if (L2) return (float)(qq + phi - 2.0 * ub) > (float)(qq + phi - 2.0 * tk);
+    return (float)ub < (float)tk;
+}
+
 // Steps 4 + margin check of the re-score, shared by rescore_rank_body and tiny_search.hpp: lane (q, slot) holds candidate ci
 // of query q with its canonical dot product and |q|^2 (fp64); rank inside the query's KL-lane group, flag, write.
 template <int KL, bool L2>
@@ -564,8 +572,11 @@ __device__ __forceinline__ void rank_flag_write(const MergeArgs& p, int64_t q, i
     }
     if (p.nflag != nullptr) {
         // Margin check.  tk = exact inner product of the k-th result; a document outside the pool has an exact
-        // inner product <= bnd + e, e = err_c |q| max|x|.  If that can reach tk the pool was not provably wide
-        // enough: flag the query (the host re-scans flagged queries with the widest lists, mips_hip.hip).
+        // inner product <= ub = bnd + e, e = err_c |q| max|x|.  If that can reach tk the pool was not provably wide
+        // enough: flag the query (the host re-scans flagged queries with the widest lists, mips_hip.hip).  The comparison
+        // is made on the float32 KEYS, as in wide_rescore_kernel: rows whose inner products differ can round to the same
+        // float32 score or distance (next to a large phi nearly all do) and are then ordered by the row number, so only a
+        // key(ub) STRICTLY worse than the k-th result's keeps every outside row out.
         double tk = 0.0, qn = 0.0;
         bool have = false;
 #pragma unroll
@@ -595,11 +606,11 @@ __device__ __forceinline__ void rank_flag_write(const MergeArgs& p, int64_t q, i
                     const double dr = sqrt(*p.dres2);
                     e += dr * sqrt(qn) + (sqrt(*p.xmax2) + dr) * sqrt(p.qerr2[q]);
                 }
-                fl = !((double)b + e < tk); // also true for NaN: never certify what cannot be compared
+                fl = !margin_key_worse<L2>((double)b + e, tk, qn, p.phi); // also true for NaN: never certify what cannot be compared
             }
             if (p.bnd2 != nullptr && have) {
                 const float b2 = p.bnd2[q];
-                if (b2 > -INFINITY) fl = fl || !((double)b2 + p.err_c2 * sqrt(qn) * sqrt(*p.xmax2) < tk);
+                if (b2 > -INFINITY) fl = fl || !margin_key_worse<L2>((double)b2 + p.err_c2 * sqrt(qn) * sqrt(*p.xmax2), tk, qn, p.phi);
             }
             p.flag[q] = fl ? 1 : 0;
             if (fl) atomicAdd(p.nflag, 1u);
