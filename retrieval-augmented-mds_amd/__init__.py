@@ -11,7 +11,7 @@ from . import _lib, faiss_shim
 from ._lib import (DTYPE_BF16, DTYPE_F32, DTYPE_FP8_E4M3, DTYPE_FP8_E4M3_DOCS, IDX_POISON, LABEL_NONE, MAX_K, MAX_K_WIDE, METRIC_IP, METRIC_L2, SEED_DOCS, SEED_QUERIES, SYNTH_GAUSS,
                    SYNTH_LATTICE, SYNTH_LATTICE_FP8, build)
 from .index import (MipsIndex, cosine_rescore, filter_ignore, l2_normalize_, merge_topk, merge_topk_packed,
-                    merge_topk_sorted_packed, rows_max_sumsq, synth_fill)
+                    merge_topk_sorted_packed, range_merge_records, rows_max_sumsq, synth_fill)
 from .mips import (KnowledgeBase, Mips, MipsArgs, MipsModelOutput, augment_xb, augment_xq, get_phi,
                    in_batch_scores, inner_product, retriever_metrics)
 from .selector import Selector
@@ -20,7 +20,7 @@ from .sharded import ShardedMipsIndex, pack_topk, shard_bounds, unpack_gathered
 __all__ = [
     "MipsIndex", "ShardedMipsIndex", "Selector", "Mips", "MipsArgs", "MipsModelOutput", "KnowledgeBase",
     "get_phi", "augment_xb", "augment_xq", "inner_product", "in_batch_scores", "retriever_metrics", "IDX_POISON",
-    "l2_normalize_", "rows_max_sumsq", "merge_topk", "merge_topk_packed", "merge_topk_sorted_packed", "filter_ignore", "cosine_rescore", "synth_fill", "shard_bounds", "pack_topk",
+    "l2_normalize_", "rows_max_sumsq", "merge_topk", "merge_topk_packed", "merge_topk_sorted_packed", "range_merge_records", "filter_ignore", "cosine_rescore", "synth_fill", "shard_bounds", "pack_topk",
     "unpack_gathered", "build", "METRIC_IP", "METRIC_L2", "MAX_K", "MAX_K_WIDE", "faiss_shim",
     "LABEL_NONE",
 ]

@@ -18,6 +18,7 @@ CSRC = os.path.join(_HERE, "csrc")
 LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmips_hip.so")
 HEADER = os.path.join(_ROOT, "include", "mips_hip.h")
+HEADER_SHARDED = os.path.join(_ROOT, "include", "mips_hip_sharded.h")  # helpers of the shard exchange (no index handle)
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -37,7 +38,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER]
+    out = [HEADER, HEADER_SHARDED]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -134,7 +135,10 @@ def _bind(lib):
         "mips_index_last_kernel": (c.c_char_p, [vp]),
         "mips_index_margin_stats": (i32, [vp, c.POINTER(i64), c.POINTER(i64), c.POINTER(i64), i32, vp]),
     }
-    for name, (res, args) in sig.items():
+    sig_sharded = {  # include/mips_hip_sharded.h
+        "mips_range_merge_records": (i32, [vp, i32, i64, i64, vp, vp, vp, i64, vp, i32, vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -152,6 +156,13 @@ EXPORTS = (
     "mips_search_wide_sel", "mips_range_search_sel",
     "mips_index_set_labels", "mips_index_read_labels", "mips_search_wide_grp", "mips_range_search_grp",
 )
+
+EXPORTS_SHARDED = ("mips_range_merge_records",)  # what include/mips_hip_sharded.h declares; the same library exports it
+
+
+def range_record_words(nq: int, stride: int) -> int:
+    """MIPS_RANGE_RECORD_WORDS of include/mips_hip_sharded.h: int64 words of a shard's range-search record."""
+    return int(nq) + 1 + int(stride) + (int(stride) + 1) // 2
 
 
 def load():

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "../../include/mips_hip.h"
+#include "../../include/mips_hip_sharded.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -26,6 +27,7 @@
 #include "resolve_kernels.hpp"
 #include "scan_kernel_wide.hpp"
 #include "range_kernels.hpp"
+#include "range_merge_kernels.hpp"
 #include "select_kernels.hpp"
 
 #include "host_state.hpp"
@@ -33,6 +35,7 @@
 #include "host_search.hpp"
 #include "host_wide.hpp"
 #include "host_range.hpp"
+#include "host_range_merge.hpp"
 
 extern "C" {
 
@@ -874,6 +877,11 @@ int mips_merge_topk_sorted_packed(const int64_t* gathered, int64_t nq, int parts
     }
     HIP_TRY(hipGetLastError());
     return MIPS_OK;
+}
+
+int mips_range_merge_records(const int64_t* gathered, int parts, int64_t nq, int64_t stride, int64_t* out_lims, float* out_scores,
+                             int64_t* out_idx, int64_t cap, int64_t* workspace, int device, void* hip_stream) {
+    return range_merge_records(gathered, parts, nq, stride, out_lims, out_scores, out_idx, cap, workspace, device, (hipStream_t)hip_stream);
 }
 
 int mips_filter_ignore(const float* scores, const int64_t* idx, const int64_t* ignore, int64_t nq, int k_fetched, int k,

@@ -401,16 +401,16 @@ class MipsIndex:
         return r
 
     def range_search_into(self, x, radius, lims, D, I, idx_offset: int = 0, force_ip: bool = False, selector=None, groups=None,
-                          group_mode: str = "exclude") -> None:
+                          group_mode: str = "exclude", sel_bit0: int = 0) -> None:
         """The non-synchronising form of range_search: the caller allocates the CUDA tensors lims (int64 [nq + 1]), D (float32
         [cap]) and I (int64 [cap]); everything is enqueued on the current stream.  lims always receives the true counts; when
         lims[-1] > cap the contents of D and I are unspecified and the call is to be repeated with larger tensors.  cap = 0
-        (empty D and I) is a counting call.  `radius` is host data (a scalar or nq values).  selector, groups and
-        group_mode: as in search_wide."""
+        (empty D and I) is a counting call.  `radius` is host data (a scalar or nq values).  selector, sel_bit0, groups and
+        group_mode: as in search_wide (a row shard passes the global selector and its first global row)."""
         import torch
 
         self._check_range()
-        sel_ptr, sel_nbits, sel_flag, sel_keep = self._sel_args(selector, 0, "range_search")
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self._sel_args(selector, sel_bit0, "range_search")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         grp_ptr, grp_mode, grp_flag, grp_keep = self._grp_args(groups, group_mode, nq, "range_search")
         r = self._radii(radius, nq)
@@ -426,7 +426,7 @@ class MipsIndex:
             if groups is not None:
                 _lib.check(self._lib.mips_range_search_grp(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
                                                            D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
-                                                           int(idx_offset), flags | sel_flag | grp_flag, sel_ptr, sel_nbits, 0, grp_ptr,
+                                                           int(idx_offset), flags | sel_flag | grp_flag, sel_ptr, sel_nbits, int(sel_bit0), grp_ptr,
                                                            grp_mode, _stream_handle(self.device)), "mips_range_search_grp")
             elif selector is None:
                 _lib.check(self._lib.mips_range_search(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
@@ -435,20 +435,20 @@ class MipsIndex:
             else:
                 _lib.check(self._lib.mips_range_search_sel(self._h, ptr, code, nq, r.ctypes.data, lims.data_ptr(),
                                                            D.data_ptr() if cap else None, I.data_ptr() if cap else None, cap,
-                                                           int(idx_offset), flags | sel_flag, sel_ptr, sel_nbits, 0,
+                                                           int(idx_offset), flags | sel_flag, sel_ptr, sel_nbits, int(sel_bit0),
                                                            _stream_handle(self.device)), "mips_range_search_sel")
         del keep, sel_keep, grp_keep
 
     def range_search(self, x, radius, idx_offset: int = 0, force_ip: bool = False, selector=None, groups=None,
-                     group_mode: str = "exclude"):
+                     group_mode: str = "exclude", sel_bit0: int = 0):
         """faiss Index.range_search(x, radius) -> (lims, D, I): every stored row whose canonical score is strictly above the
         radius (inner product; L2: whose distance |q|^2 + phi - 2 q.x is strictly below it).  `radius` is a scalar or nq
         values.  The hits of query j are D / I [lims[j] : lims[j + 1]], in ascending row order; lims is int64 [nq + 1].
         NumPy in -> NumPy out; torch CUDA tensor in -> torch CUDA tensors out.  The result's size is not known beforehand: a
         first call runs with a guessed capacity, lims[-1] is READ ON THE HOST -- THIS SYNCHRONISES the stream -- and one repeat
         with the exact size follows if the guess was too small (range_search_into is the form that never synchronises).
-        bf16 and f32 indexes of at most 1024 columns.  selector (as in search_wide): only selected rows can be hits; groups
-        and group_mode (as in search_wide): only rows the group rule admits for the query."""
+        bf16 and f32 indexes of at most 1024 columns.  selector and sel_bit0 (as in search_wide): only selected rows can be hits;
+        groups and group_mode (as in search_wide): only rows the group rule admits for the query."""
         import torch
 
         from .selector import Selector
@@ -467,7 +467,7 @@ class MipsIndex:
             D = torch.empty(cap, dtype=torch.float32, device=dev)
             I = torch.empty(cap, dtype=torch.int64, device=dev)
             self.range_search_into(keep, r, lims, D, I, idx_offset=idx_offset, force_ip=force_ip, selector=selector, groups=groups,
-                                   group_mode=group_mode)
+                                   group_mode=group_mode, sel_bit0=sel_bit0)
             total = int(lims[-1].item())   # the synchronisation
             if total <= cap:
                 break
@@ -746,6 +746,43 @@ def merge_topk_sorted_packed(gathered, nq: int, parts: int, k: int, metric: int 
     _lib.check(lib.mips_merge_topk_sorted_packed(gathered.data_ptr(), nq, parts, k, metric, out_s.data_ptr(), out_i.data_ptr(),
                                                  dev, _stream_handle(dev)), "mips_merge_topk_sorted_packed")
     return out_s, out_i
+
+
+def range_merge_records(gathered, parts: int, nq: int, stride: int, cap: int | None = None, out=None):
+    """Device merge of the range-search records of `parts` row shards (include/mips_hip_sharded.h, mips_range_merge_records):
+    gathered is a CUDA int64 tensor of parts * range_record_words(nq, stride) words, the records end to end in ascending row
+    order of their shards, as an all-gather leaves them.  -> (lims int64 [nq + 1], D float32 [cap], I int64 [cap]) CUDA tensors;
+    nothing synchronises.  lims holds the true global counts; D and I are complete iff lims[-1] <= cap and no part exceeded its
+    stride.  cap = None: parts * stride, which no result of untruncated parts exceeds; cap = 0 only counts.  out = (lims, D, I):
+    the caller's contiguous CUDA tensors of those dtypes are written instead (cap is then len(D) = len(I)) and returned."""
+    import torch
+
+    lib = _lib.load()
+    parts, nq, stride = int(parts), int(nq), int(stride)
+    words = _lib.range_record_words(nq, stride)
+    if not (isinstance(gathered, torch.Tensor) and gathered.is_cuda and gathered.dtype == torch.int64 and gathered.is_contiguous()):
+        raise ValueError("range_merge_records: gathered must be a contiguous CUDA int64 tensor")
+    if parts < 1 or nq < 0 or stride < 0 or gathered.numel() != parts * words:
+        raise ValueError(f"range_merge_records: {gathered.numel()} words for {parts} records of {words}")
+    dev = gathered.device.index
+    if out is not None:
+        lims, D, I = out
+        for t, dt, n in ((lims, torch.int64, nq + 1), (D, torch.float32, None), (I, torch.int64, D.shape[0])):
+            if not (isinstance(t, torch.Tensor) and t.device == gathered.device and t.dtype == dt and t.dim() == 1 and t.is_contiguous()
+                    and (n is None or t.shape[0] == n)):
+                raise ValueError(f"range_merge_records: out must be contiguous 1-d tensors on {gathered.device}: int64 [nq + 1], "
+                                 "float32 [cap], int64 [cap]")
+        cap = int(D.shape[0])
+    else:
+        cap = parts * stride if cap is None else int(cap)
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=gathered.device)
+        D = torch.empty(cap, dtype=torch.float32, device=gathered.device)
+        I = torch.empty(cap, dtype=torch.int64, device=gathered.device)
+    work = torch.empty(parts * nq, dtype=torch.int64, device=gathered.device)
+    _lib.check(lib.mips_range_merge_records(gathered.data_ptr(), parts, nq, stride, lims.data_ptr(), D.data_ptr() if cap else None,
+                                            I.data_ptr() if cap else None, cap, work.data_ptr() if nq else None, dev,
+                                            _stream_handle(dev)), "mips_range_merge_records")
+    return lims, D, I   # (the workspace goes back to the allocator of the stream the kernels run on: stream-ordered reuse)
 
 
 def merge_topk(cand_s, cand_i, parts: int, k: int, metric: int = _lib.METRIC_IP):

@@ -10,6 +10,10 @@ The all-gather payload is one int64 tensor [nq, k, 2] per rank (float32 score bi
 4096 x 5 x 16 B = 320 KiB at the headline config -- latency bound on xGMI.  The wide search (search_wide, 30 <= k <= 1024)
 takes the same route with a payload that is bandwidth-sized instead: 6.5 MB per rank at 4096 x 100, 64 MiB at 4096 x 1024, and
 the gathered buffer is `world` times that.
+
+The range search (range_search) has a result of variable size: every rank searches into ONE int64 record -- lims, global ids and
+scores side by side (range_record_views; include/mips_hip_sharded.h) -- the ranks agree on a common record size with one scalar
+all-reduce, the records travel in the same ONE all-gather, and a replicated merge lays the shards' segments end to end per query.
 """
 from __future__ import annotations
 
@@ -45,6 +49,16 @@ def unpack_gathered(gathered, world: int):
     return s, g[..., 1].contiguous()
 
 
+def range_record_views(rec, nq: int, stride: int):
+    """The three regions of a range-search record (a contiguous int64 torch tensor of range_record_words(nq, stride) words) as
+    contiguous 1-d views: lims int64 [nq + 1], D float32 [stride], I int64 [stride] -- what MipsIndex.range_search_into takes."""
+    import torch
+
+    if rec.dtype != torch.int64 or rec.dim() != 1 or not rec.is_contiguous() or rec.shape[0] != _lib.range_record_words(nq, stride):
+        raise ValueError(f"range_record_views: expected {_lib.range_record_words(nq, stride)} contiguous int64 words")
+    return rec[:nq + 1], rec[nq + 1 + stride:].view(torch.float32)[:stride], rec[nq + 1:nq + 1 + stride]
+
+
 class ShardedMipsIndex:
     """One logical exact index, row-sharded across the ranks of a torch.distributed group.
 
@@ -53,11 +67,15 @@ class ShardedMipsIndex:
     all-gather + unpack plumbing can be exercised with the gloo backend on CPU-only machines, where
     tests substitute the CPU oracle for the two device steps.  local_search_wide(q, k, idx_offset) is the
     local step of search_wide (default MipsIndex.search_wide); when only one of the two local steps is
-    injected it stands in for the other.
+    injected it stands in for the other.  local_range_search(q, radius, idx_offset, **kw) -> NumPy (lims, D, I) and
+    range_merge(gathered, parts, nq, stride) -> (lims, D, I) are the two steps of range_search (defaults
+    MipsIndex.range_search_into / mips_range_merge_records); kw carries force_ip, selector + sel_bit0, groups + group_mode when
+    the call has them, `gathered` is a NumPy int64 array of the records end to end.  With an injected local step the record is
+    assembled on the host.
     """
 
     def __init__(self, d: int, metric: int = _lib.METRIC_IP, dtype: str = "bf16", group=None, device=None,
-                 local_search=None, merge=None, local_search_wide=None):
+                 local_search=None, merge=None, local_search_wide=None, local_range_search=None, range_merge=None):
         import torch.distributed as dist
 
         self.d = int(d)
@@ -68,7 +86,9 @@ class ShardedMipsIndex:
         self.ntotal_global = 0
         self.lo = self.hi = 0
         self.local = None
-        if local_search is None and local_search_wide is None:
+        self._local_range_search = local_range_search
+        self._range_merge = range_merge
+        if local_search is None and local_search_wide is None and local_range_search is None:
             from .index import MipsIndex
 
             self.local = MipsIndex(d, metric=metric, dtype=dtype, device=device)
@@ -375,6 +395,151 @@ class ShardedMipsIndex:
             return merge_topk_sorted_packed(gathered, nq, self.world, k, metric)
         s, i = self._local_search_wide(q, k, self.lo, **({"force_ip": True} if force_ip else {}), **sel_kw)
         return self._exchange(s, i, k, metric)
+
+    # ------------------------------------------------------------------ range search
+    @staticmethod
+    def _range_stride_guess(nq: int) -> int:
+        """Room for hits in the first local call of range_search: MipsIndex.range_search's guess, the same on every rank."""
+        return max(1 << 16, 256 * int(nq))
+
+    def _range_kw(self, what: str, idx_offset: int, force_ip: bool, selector, groups, group_mode: str) -> dict:
+        """Checks shared by the two range calls; -> the keywords of the local step."""
+        if idx_offset:
+            raise ValueError(f"ShardedMipsIndex.{what} returns global row numbers; idx_offset must be 0")
+        if self.local is not None:
+            self.local._check_range()  # e4m3 storage, more than 1024 columns: refused as MipsIndex refuses them
+        kw = {"force_ip": True} if force_ip else {}
+        if selector is not None:
+            from .selector import Selector
+
+            if self.local is not None and not (isinstance(selector, Selector) or (isinstance(selector, np.ndarray) and selector.dtype == np.uint8)):
+                selector = Selector.from_mask(selector, device=self.local.device)  # packed once for the repeat call
+            nbits = selector.nbits if isinstance(selector, Selector) else (
+                8 * selector.size if isinstance(selector, np.ndarray) and selector.dtype == np.uint8 else len(selector))
+            if nbits < self.ntotal_global:
+                raise ValueError(f"{what}: the selector has {nbits} bits, the sharded index {self.ntotal_global} rows")
+            kw.update(selector=selector, sel_bit0=self.lo)
+        if groups is not None:
+            kw.update(groups=groups, group_mode=group_mode)
+        return kw
+
+    def _range_home(self):
+        """Where this rank's record is written and merged: the shard's GPU; the host when both steps are injected."""
+        import torch
+
+        if self.local is not None:
+            return torch.device("cuda", self.local.device)
+        return torch.device("cuda") if self._range_merge is None else torch.device("cpu")
+
+    def _range_local_record(self, q, r, nq: int, stride: int, kw: dict):
+        """This shard's hits as a record of `stride` entries on _range_home().  The lims are the true counts whatever the stride
+        is; entries past it are dropped, as mips_range_search drops them."""
+        import torch
+
+        home = self._range_home()
+        if self._local_range_search is None:
+            rec = torch.empty(_lib.range_record_words(nq, stride), dtype=torch.int64, device=home)
+            lims, D, I = range_record_views(rec, nq, stride)
+            self.local.range_search_into(q, r, lims, D, I, idx_offset=self.lo, **kw)
+            return rec
+        hq = q.detach().cpu().numpy() if isinstance(q, torch.Tensor) else q
+        lims, D, I = self._local_range_search(hq, r, self.lo, **kw)
+        rec = torch.zeros(_lib.range_record_words(nq, stride), dtype=torch.int64)
+        v_lims, v_D, v_I = range_record_views(rec, nq, stride)
+        m = min(stride, len(I))
+        v_lims.copy_(torch.from_numpy(np.ascontiguousarray(lims, dtype=np.int64)))
+        v_D[:m].copy_(torch.from_numpy(np.ascontiguousarray(D[:m], dtype=np.float32)))
+        v_I[:m].copy_(torch.from_numpy(np.ascontiguousarray(I[:m], dtype=np.int64)))
+        return rec.to(home)
+
+    def _range_gather(self, rec):
+        """The ONE collective of the range calls: this rank's record in, the records end to end out -- as they arrived (on the
+        host under gloo, which moves host memory) and on the record's own device."""
+        import torch
+        import torch.distributed as dist
+
+        home = rec.device
+        if dist.get_backend(self.group) == "gloo" and rec.is_cuda:
+            rec = rec.cpu()
+        arrived = torch.empty(self.world * rec.shape[0], dtype=torch.int64, device=rec.device)
+        dist.all_gather_into_tensor(arrived, rec, group=self.group)
+        return arrived, (arrived if arrived.device == home else arrived.to(home))
+
+    def range_search(self, q, radius, idx_offset: int = 0, force_ip: bool = False, selector=None, groups=None, group_mode: str = "exclude"):
+        """MipsIndex.range_search over the row shards: replicated queries and radii in, (lims, D, I) with global row numbers out,
+        the same on every rank; hits of a query in ascending row order.  NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors
+        out.  idx_offset must be 0; force_ip, selector (GLOBAL, one bit per global row, the same on every rank), groups /
+        group_mode (replicated like the queries, against set_labels_global) as in search_wide.  bf16 and f32 shards of at most
+        1024 columns.  COLLECTIVE and SYNCHRONISING: every shard searches into a record with MipsIndex.range_search's guess of
+        a capacity, ONE scalar all-reduce (MAX) of the shards' totals is read on the host, a shard that found more than its
+        record holds repeats its search once with that maximum, every record is brought to that common size, ONE all-gather
+        moves the records and mips_range_merge_records lays the shards' segments end to end per query."""
+        import torch
+        import torch.distributed as dist
+
+        from .index import MipsIndex, range_merge_records
+
+        kw = self._range_kw("range_search", idx_offset, force_ip, selector, groups, group_mode)
+        as_numpy = not isinstance(q, torch.Tensor)
+        if self.world == 1:
+            if self._local_range_search is None:
+                return self.local.range_search(q, radius, self.lo, **kw)
+            return self._local_range_search(q.detach().cpu().numpy() if not as_numpy else q, radius, self.lo, **kw)
+        nq = int(q.shape[0])
+        r = MipsIndex._radii(radius, nq)
+        stride = int(self._range_stride_guess(nq))
+        rec = self._range_local_record(q, r, nq, stride, kw)
+        # the shards' totals: one scalar all-reduce, read on the host -- the call's synchronisation
+        if dist.get_backend(self.group) == "nccl":
+            total = rec[nq:nq + 1].clone()
+            dist.all_reduce(total, op=dist.ReduceOp.MAX, group=self.group)
+            common, own = (int(v) for v in torch.cat((total, rec[nq:nq + 1])).tolist())
+        else:
+            total = rec[nq:nq + 1].to("cpu", copy=True)  # (a copy also of a host record: the all-reduce writes in place)
+            own = int(total.item())
+            dist.all_reduce(total, op=dist.ReduceOp.MAX, group=self.group)
+            common = int(total.item())
+        if own > stride:  # the guess was too small HERE: once more, with room for the largest shard result
+            stride = common
+            rec = self._range_local_record(q, r, nq, stride, kw)
+        if stride != common:  # the record at the common size: the lims and the `own` entries that count
+            fit = torch.empty(_lib.range_record_words(nq, common), dtype=torch.int64, device=rec.device)
+            for dst, src, n in zip(range_record_views(fit, nq, common), range_record_views(rec, nq, stride), (nq + 1, own, own)):
+                dst[:n].copy_(src[:n])
+            rec = fit
+        arrived, gathered = self._range_gather(rec)
+        if self._range_merge is None:
+            cap = int(arrived.view(self.world, -1)[:, nq].sum().item())  # (on the host already under gloo)
+            lims, D, I = range_merge_records(gathered, self.world, nq, common, cap)
+        else:
+            lims, D, I = self._range_merge(arrived.cpu().numpy(), self.world, nq, common)
+        out = (lims, D, I)
+        if as_numpy:
+            return tuple(t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in out)
+        return tuple(t if isinstance(t, torch.Tensor) and t.device == q.device else torch.as_tensor(t).to(q.device) for t in out)
+
+    def range_search_into(self, q, radius, lims, D, I, part_cap: int, idx_offset: int = 0, force_ip: bool = False, selector=None,
+                          groups=None, group_mode: str = "exclude") -> None:
+        """The form of range_search that never synchronises on the GPU: every shard searches into a record of `part_cap` entries,
+        then ONE all-gather and ONE merge into the caller's CUDA tensors lims (int64 [nq + 1]), D (float32 [cap]) and I (int64
+        [cap]).  lims receives the true global counts whatever happens; D and I are valid iff no shard found more than part_cap
+        hits and lims[-1] <= cap -- the caller reads lims when it needs to know, and a shard's own count is lims of
+        local.range_search_into.  Device steps only (no injection); under gloo the all-gather is host-staged, which waits for
+        the record."""
+        import torch
+
+        from .index import MipsIndex, range_merge_records
+
+        kw = self._range_kw("range_search_into", idx_offset, force_ip, selector, groups, group_mode)
+        if self.local is None or self._range_merge is not None:
+            raise ValueError("range_search_into runs the library's own device steps; injected steps serve range_search only")
+        if self.world == 1:
+            return self.local.range_search_into(q, radius, lims, D, I, idx_offset=self.lo, **kw)
+        nq, part_cap = int(q.shape[0]), int(part_cap)
+        if part_cap < 0:
+            raise ValueError("range_search_into: part_cap must be >= 0")
+        rec = self._range_local_record(q, MipsIndex._radii(radius, nq), nq, part_cap, kw)
+        range_merge_records(self._range_gather(rec)[1], self.world, nq, part_cap, out=(lims, D, I))
 
     def _search_force_ip(self, q, k: int):
         s, i = self.local.search(q, k, self.lo, force_ip=True)
