@@ -421,7 +421,8 @@ int mips_index_check_error(mips_index_t* index, int synchronize, void* hip_strea
  * best MFMA score B anything OUTSIDE the pool can have had (unpopped list entries, documents rejected by an insert
  * bound, documents dropped from a full running list) and FLAGS the query when B + e >= tk, e = d 2^-23 |q| max|x|
  * (a rigorous bound for fp32 accumulation of the exact bf16 / e4m3 products).  "margin_check" (mips_index_set_param):
- *   0  off (an fp32-exact index then always runs the three-segment scan);
+ *   0  off (an fp32-exact index then always runs the three-segment scan; the bf16 scan at row pitch 768 beyond 256 queries with
+ *      k <= 5 keeps running lists of 4, so a query whose five best rows all fall into one of its 4 nsplit lists then loses one);
  *   1  (default) CERTIFY: flagged queries are settled EXACTLY -- one pass over the stored rows per 16 flagged queries (8 on the
  *      e4m3 indexes) computes canonical scores by brute force (csrc/resolve_kernels.hpp: of every row whose MFMA score comes
  *      within the error bound of the current k-th key; on the e4m3 indexes, and with "resolve" = 2, of every row) and the rows

@@ -11,7 +11,8 @@
 //     two MFMAs (one per query block), 4 accumulator registers each -> 8 accumulator VGPRs instead of 16,
 //     which pays for the second running list a lane now needs (lane (c, g) sees documents 4 g .. 4 g + 3 of
 //     each half for queries c and 16 + c); the half-block epilogue is a handful of instructions unless a
-//     document passes (16 accumulators and one epilogue per block do not fit: 13+ spilled registers);
+//     document passes (16 accumulators and one epilogue per block do not fit next to lists of 6: 13+ spilled
+//     registers -- the pitch-768 shared-block instance runs them next to lists of 4, see ONE_PASS below);
 //   * four lanes (g = 0..3) share a query, so a (query, split) pair has 4 sub-lists of KL entries.  A
 //     document of global rank r can only be pushed out of its sub-list by KL better documents of the same
 //     sub-list, so ranks 1 .. KL survive for certain (KL = 6 = k + 1 for k <= 5), the re-score pool is the
@@ -59,6 +60,14 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     static_assert(KL <= 8, "8 class words vouch for 8 documents");
     static_assert(PUB >= 1 && PUB <= KL, "a sub-list publishes one of its entries");
     constexpr int STEPS = 2 * KS32; // k32-steps per block (two halves)
+    // ONE_PASS (the pitch-768 shared-block instance with pools of 8): the accumulators of BOTH halves stay live through the
+    // chain and the block runs one pre-test, one ballot and one branch instead of two.  The eight extra accumulator registers
+    // are paid for by keeping the sub-lists KLI = 4 deep in registers; the record a lane writes still has KL slots (below).
+    // A list of 4 may drop a true top-5 member: its 4th score then bounds what it dropped, the margin check flags the query
+    // and the exact pass settles it, exactly as for any other pool that was not provably wide enough.
+    constexpr bool ONE_PASS = KL == 6 && KS32 == 24 && !NT_DOCS && PUB == 1;
+    constexpr int KLI = ONE_PASS ? 4 : KL; // entries a sub-list keeps while it scans
+    static_assert(PUB <= KLI, "a sub-list publishes one of the entries it keeps");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -92,14 +101,14 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
 #endif
     }
 
-    float ls[2][KL];
-    int li[2][KL];
+    float ls[2][KLI];
+    int li[2][KLI];
     float thr[2];
 #pragma unroll
     for (int n = 0; n < 2; ++n) {
         thr[n] = -INFINITY;
 #pragma unroll
-        for (int i = 0; i < KL; ++i) {
+        for (int i = 0; i < KLI; ++i) {
             ls[n][i] = -INFINITY;
             li[n][i] = IDX_NONE;
         }
@@ -125,15 +134,27 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     // ---- LDS-DMA map (as v3): piece pc = slab * 4 + rg, 8 rows x 128 B
     const unsigned char* docs_b = reinterpret_cast<const unsigned char*>(p.docs);
     const int64_t row_bytes = (int64_t)p.ld * 2;
+    // ONE_PASS keeps the per-lane source offset of issue_piece in a register (the shorter lists leave room for it); the asm
+    // makes the value opaque, so that it is not re-derived from the lane id at each of the six pieces of a block
+    unsigned lane_off_kept = 0u;
+    if constexpr (ONE_PASS) {
+        lane_off_kept = ((unsigned)lane >> 3) * (unsigned)row_bytes + ((((unsigned)lane & 7u) ^ (((unsigned)lane >> 4) & 7u)) << 4);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(lane_off_kept));
+#endif
+    }
     auto issue_piece = [&](const unsigned char* blk_base, int stage, int i) {
         const __amdgpu_buffer_rsrc_t rsrc =
             __builtin_amdgcn_make_buffer_rsrc((void*)blk_base, 0, (int)(V3_DB * row_bytes), 0x00020000);
         const int pc = wave + WAVES * i;
         const int slab = pc >> 2, rg = pc & 3;
-        // per-lane source offset, recomputed per piece from the lane id (the kernel has no VGPR to spare):
-        // row lane >> 3 of the piece, chunk slot (lane & 7) ^ ((row >> 1) & 7) = (lane & 7) ^ ((4 rg + (lane >> 4)) & 7)
-        const unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const unsigned lane_off0 = (ln >> 3) * (unsigned)row_bytes + (((ln & 7u) ^ ((ln >> 4) & 7u)) << 4);
+        // per-lane source offset: row lane >> 3 of the piece, chunk slot (lane & 7) ^ ((row >> 1) & 7) = (lane & 7) ^
+        // ((4 rg + (lane >> 4)) & 7).  Recomputed per piece from the lane id where the kernel has no VGPR to spare
+        unsigned lane_off0 = lane_off_kept;
+        if constexpr (!ONE_PASS) {
+            const unsigned ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            lane_off0 = (ln >> 3) * (unsigned)row_bytes + (((ln & 7u) ^ ((ln >> 4) & 7u)) << 4);
+        }
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void*)(smem + stage * STAGE_BYTES + pc * 1024), 16,
                                                  (rg & 1) ? (lane_off0 ^ 64u) : lane_off0,
                                                  rg * 8 * (int)row_bytes + slab * 128, 0, NT_DOCS ? 2 : 0);
@@ -192,8 +213,45 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
                 for (int r = 0; r < 4; ++r) {
                     const float s = acc[n][r];
                     if (s > thr[n]) {
-                        list_insert<KL>(ls[n], li[n], s, base + r);
-                        thr[n] = fmaxf(thr[n], ls[n][KL - 1]);
+                        list_insert<KLI>(ls[n], li[n], s, base + r);
+                        thr[n] = fmaxf(thr[n], ls[n][KLI - 1]);
+                    }
+                }
+                if (ls[n][PUB - 1] > mark) { // new PUB-th best of this sub-list: raise its class word, (4 split + g) & 7
+                    const unsigned cls = (4u * (unsigned)split + ((thr_addr >> 8) & 3u)) & 7u;
+                    publish_umax(thr_encode(ls[n][PUB - 1]), (thr_addr & ~0x3FFu) + ((thr_addr & 0xF0u) << 1) + 512u * n + 4u * cls, thr_rsrc);
+                }
+            }
+        }
+    };
+
+    // ONE_PASS: epilogue of the whole 32-document block.  acc[half][n] = documents 16 half + 4 g .. + 3 against query 16 n + c.
+    // The fast path (8 max, 2 compares, one branch) falls through; the insert path is one loop per query that visits only the
+    // accumulators above the bound, lowest document first (the order the strict-'>' tie rule needs), through ONE copy of
+    // list_insert -- a select chain picks the score, so the path stays a few hundred bytes instead of sixteen inlined inserts.
+    auto epilogue_block = [&](f32x4 (&acc)[2][2], int blk) {
+        const float mx0 = fmaxf(fmaxf(fmaxf(acc[0][0][0], acc[0][0][1]), fmaxf(acc[0][0][2], acc[0][0][3])),
+                                fmaxf(fmaxf(acc[1][0][0], acc[1][0][1]), fmaxf(acc[1][0][2], acc[1][0][3])));
+        const float mx1 = fmaxf(fmaxf(fmaxf(acc[0][1][0], acc[0][1][1]), fmaxf(acc[0][1][2], acc[0][1][3])),
+                                fmaxf(fmaxf(acc[1][1][0], acc[1][1][1]), fmaxf(acc[1][1][2], acc[1][1][3])));
+        if (__builtin_expect(__ballot((int)(mx0 > thr[0]) | (int)(mx1 > thr[1])) != 0ull, 0)) { // '|': no lane-level short circuit
+            const unsigned thr_addr = thr_addr_of(lane_id_here());
+            const int base = blk * V3_DB + (int)((thr_addr >> 6) & 12u); // + 4 g, from the lane bits
+#pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                const float mark = ls[n][PUB - 1];
+                unsigned m = 0u; // bit 4 half + r: that accumulator is above the bound
+#pragma unroll
+                for (int e = 0; e < 8; ++e) m |= acc[e >> 2][n][e & 3] > thr[n] ? 1u << e : 0u;
+                while (m != 0u) {
+                    const int e = __ffs(m) - 1;
+                    m &= m - 1u;
+                    float s = acc[0][n][0];
+#pragma unroll
+                    for (int x = 1; x < 8; ++x) s = e == x ? acc[x >> 2][n][x & 3] : s;
+                    if (s > thr[n]) { // the bound may have risen since the mask was taken
+                        list_insert<KLI>(ls[n], li[n], s, base + 16 * (e >> 2) + (e & 3));
+                        thr[n] = fmaxf(thr[n], ls[n][KLI - 1]);
                     }
                 }
                 if (ls[n][PUB - 1] > mark) { // new PUB-th best of this sub-list: raise its class word, (4 split + g) & 7
@@ -225,9 +283,19 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
         refresh_thresholds(refresh); // first VMEM op of the block
         __builtin_amdgcn_sched_barrier(0);
         const bool ragged = (int64_t)(blk + 1) * V3_DB > p.ntotal; // uniform
+        auto mask_ragged = [&](f32x4 (&a)[2], int half) { // last block of the index only: rows past the end score -inf
+            const int base = blk * V3_DB + 16 * half + 4 * (int)(lane_id_here() >> 4);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                if ((int64_t)(base + r) >= p.ntotal) {
+                    a[0][r] = -INFINITY;
+                    a[1][r] = -INFINITY;
+                }
+        };
+        f32x4 accs[2][2]; // [half][n]; without ONE_PASS a half's accumulators die in its own epilogue
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
-            f32x4 acc[2];
+            f32x4(&acc)[2] = accs[half];
 #pragma unroll
             for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -262,16 +330,17 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
                     thr[n] = fmaxf(thr[n], key > 1u ? thr_decode(key - 1u) : -INFINITY);
                 }
             }
-            if (ragged) { // last block of the index only
-                const int base = blk * V3_DB + 16 * half + 4 * (int)(lane_id_here() >> 4);
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    if ((int64_t)(base + r) >= p.ntotal) {
-                        acc[0][r] = -INFINITY;
-                        acc[1][r] = -INFINITY;
-                    }
+            if constexpr (!ONE_PASS) {
+                if (ragged) mask_ragged(acc, half);
+                epilogue_half(acc, blk, half);
             }
-            epilogue_half(acc, blk, half);
+        }
+        if constexpr (ONE_PASS) { // after arrive() and the bound refresh: one top-k pass over both halves
+            if (ragged) {
+                mask_ragged(accs[0], 0);
+                mask_ragged(accs[1], 1);
+            }
+            epilogue_block(accs, blk);
         }
     };
 
@@ -304,10 +373,18 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     for (int n = 0; n < 2; ++n) {
         const int q = qt * TN + wave * 32 + n * 16 + c;
         const size_t o = (((size_t)q * p.nsplit + split) * 4 + g) * KL;
+        // The record keeps KL slots per list.  A list of KLI < KL entries repeats its last entry in the slots it does not
+        // have.  What merge_select_body (aux_kernels.hpp) makes of that:
+        //   * its bound on what a full list dropped is the list's LAST slot when that slot holds a row: here the KLI-th
+        //     score of a list that filled -- every row this list pushed out or refused scored no more than that -- and
+        //     (-inf, IDX_NONE) for a list that never filled, which dropped nothing and leaves the bound alone;
+        //   * the repeats add no candidate: the slots of one list go to consecutive lanes of the merge, so the copies of
+        //     an entry sit in different lanes' lists; when the entry is the wave-wide best every lane that holds it has it
+        //     at its head and pops it in the same round, and the round counts once.  The pool holds each row once.
 #pragma unroll
         for (int i = 0; i < KL; ++i) {
-            p.part_s[o + i] = ls[n][i];
-            p.part_i[o + i] = li[n][i];
+            p.part_s[o + i] = ls[n][i < KLI ? i : KLI - 1];
+            p.part_i[o + i] = li[n][i < KLI ? i : KLI - 1];
         }
     }
 }
