@@ -1,7 +1,10 @@
 // Host side of libmips_hip.so, part 2 of 3 (included by mips_hip.hip): which scan kernel answers which search -- the instance
-// tables (one row per shipped scan-kernel instance, every family), and launch_search<K'> in three steps with a plain struct
-// between them: choose_scan (no HIP calls: kernel row, tiles, lists, splits, XCD groups, grid), launch_scan (the ONE place that
-// launches a scan kernel) and launch_tail (merge_select -> rescore_rank with the margin check).  DESIGN.md section 4, "Dispatch".
+// tables (one row per shipped scan-kernel instance, every family), pool_policy (no HIP calls: the ONE place that decides which
+// pool the first scan of a search selects from -- K', two-stage, optimistic -- and counts fast_skip down) and launch_search<K'>
+// in three steps with a plain struct between them: choose_scan (no HIP calls: kernel row, tiles, lists, splits, XCD groups, grid),
+// launch_scan (the ONE place that launches a scan kernel) and launch_tail (merge_select -> rescore_rank with the margin check).
+// All of them read the launch's view of the index, its staged queries and its switches from the SearchCall they are handed,
+// and write nothing on the index but scratch, statistics, the event ring and last_kernel.  DESIGN.md section 4, "Dispatch".
 #pragma once
 
 namespace {
@@ -152,37 +155,103 @@ struct ScanPlan {
     size_t ncand;            // candidates per query in the lists: nsplit * lists * list_len
 };
 
+// ---- Which pool a search selects from: ONE policy, no HIP calls.  pool_policy maps (index, nq, k, outputs, split, margin mode,
+// knobs, fast_skip) to the list length K' of the first scan and to what is optimistic about it; search_impl switches on K',
+// choose_scan reads SearchCall::optimistic and only picks the instance.
+struct PoolPolicy {
+    int kl;          // K' = 8 / 10 / 16 / 32 >= k + 3: the pool merge_select hands to the exact re-score
+    bool fast;       // stage 1 of the two-stage search of an fp32-exact index (scan of the bf16 rows_hi)
+    bool optimistic; // the scan takes its pool from sub-lists (scan_kernel_v4 / k3), not from true K'-entry lists
+    bool recheck;    // fast or a pool picked for optimism: flagged queries get a second scan with true K' = 32 lists whatever K'
+                     // was, and a synchronising call that flags too many of them starts the fast_skip countdown
+};
+// row pitches of scan_kernel_v4 (16x16x32 MFMA shape, sub-lists of 6): 384 .. 768 (at 256 the shorter chain no longer pays:
+// 2.03 vs 2.00 ms).  With pitch 1024 beyond 256 queries (scan_kernel_k3) these are the optimistic pitch windows
+inline bool v4_pitch(int ld) { return ld % 128 == 0 && ld >= 384 && ld <= 768; }
+
+// The MFMA scores only SELECT a pool of K' candidates that is then re-scored exactly.  What is GUARANTEED
+// to reach the pool per (query, split): the 32x32 kernels (scan_kernel_v3 / f8 / generic) keep lists of K' entries, so MFMA
+// ranks 1 .. K'; the 16x16 kernels (scan_kernel_v4 / f8x: bf16 pitch 384 .. 768 or fp8 pitch <= 768, k <= 5, more than one
+// query tile) keep 4 sub-lists of 6, so MFMA ranks 1 .. 6 = k + 1 for certain and 7 .. 8 unless 6 better documents share the
+// sub-list (rows congruent mod 16 within a split).  Queries whose k-th exact score is too close to what the pool may have lost
+// are detected by the re-score and settled by finish_margin.
+inline PoolPolicy pool_policy(mips_index* ix, int64_t nq, int k, bool out_dev, bool split, int margin) {
+    const bool certifies = call_certifies(margin, out_dev) && !split; // (split tail: the certificate, if any, is part of the tail)
+    const bool bf16_rows = ix->plane == 0 && ix->esize == 2 && !ix->mixed;
+    const bool knob = ix->opt_f32_fast != 0; // "f32_fast" / "optimistic": one switch for all three below
+    // fp32-exact index: two-stage search when the call may synchronise anyway (see mips_index: rows_hi), or always
+    // ("f32_fast" = 2).  Stage 1 keeps K' = 32 lists where the bf16 kernels have them (pitch 256 / 512 / 768): the pool's bound
+    // is then the ~33rd best score, far enough below the k-th for the widened margin to certify nearly every query on
+    // well-separated data (with K' = 8 pools 44 % of the queries of a Gaussian test set went to the second stage).
+    // (round 3: row pitch 1024 has true K' = 32 lists as well -- with pools of 8, all it had before, 46 % of a Gaussian test set
+    // went to the second stage and stage 1 did not pay)
+    // k <= 13 only: the pool is 32 wide whatever k, and the widened margin (representation error of bf16(x) . bf16(q)) has to
+    // fit between the k-th and the 33rd score -- at k = 20 .. 29 nearly every query of a Gaussian test set was flagged, and an
+    // exact pass per 8 flagged queries costs far more than the three-segment scan saves.
+    // (pools of 32, not 16: with the 16th best score as the bound 30 of 4096 Gaussian queries went to the second stage, and a
+    // second stage of even one query tile costs more than stage 1 saved -- 22 ms per call instead of 5.4)
+    const bool fast = ix->plane > 0 && ix->hp > 0 && ix->hp <= 1024 && k <= 13 && knob && margin != 0 && !split &&
+                      (ix->opt_f32_fast == 2 || certifies);
+    // bf16 rows at pitch 1024, k <= 5, a large index, a call that certifies: pool of 16 (scan_kernel_k3 with every sub-list
+    // vouching for its 2nd best).  The MFMA error bound at K = 1024 (0.14 on unit-variance data) reaches from the 5th exact score
+    // to the 8th best approximate one for one Gaussian query in ~3000 at 2^22 rows, and each flagged query costs a pass over the
+    // index (3 ms there); the 16th best is out of reach.  Small indexes keep the pool of 8 (their exact pass is cheap), and so
+    // do forced kernels.
+    const bool deep_1024 = k <= 5 && bf16_rows && ix->ld == 1024 && nq > 256 && ix->ntotal >= (1ll << 21) && certifies && knob &&
+                           ix->opt_variant == 0;
+    // bf16 index, a call that certifies, 8 <= k <= 29: pool of 32 out of the 16x16x32 kernel's sub-lists (round 3: k = 14 .. 29
+    // as well -- the class words vouch for 32 documents, what the sub-lists of 6 may have dropped is bounded, the margin check
+    // decides per query; at pitch 1024 out of scan_kernel_k3's, every sub-list vouching for its 4th best).
+    const bool opt = k > 7 && bf16_rows && certifies && knob && (v4_pitch(ix->ld) || (ix->ld == 1024 && nq > 256));
+    // At most one of the three holds (fp32-exact index / k <= 5 / k >= 8).  The optimistic scan pays while few queries need the
+    // second one: a call that sent too many there (scan_and_finish) has the next ones skip it -- "f32_fast" = 2 never counts down
+    // (setting the knob clears fast_skip, and scan_and_finish does not arm it then)
+    bool recheck = fast || deep_1024 || opt;
+    if (recheck && ix->opt_f32_fast == 1 && ix->fast_skip > 0) {
+        --ix->fast_skip;
+        recheck = false;
+    }
+    PoolPolicy p;
+    p.fast = fast && recheck;
+    p.recheck = recheck;
+    // sub-list pools exist at the optimistic pitch windows of the SCANNED rows, and forced kernels ("variant") keep true lists
+    const int pitch = p.fast ? ix->hp : ix->ld;
+    p.optimistic = recheck && ix->opt_variant == 0 && (v4_pitch(pitch) || (pitch == 1024 && nq > 256));
+    // k + 1 = 6 is what Mips.search fetches for top_k = 5 with ignore_indexes (mips.py:388-398): K' = 10 serves k <= 7
+    p.kl = p.fast ? 32 : k <= 5 ? (recheck ? 16 : 8) : k <= 7 ? 10 : (recheck || k > 13) ? 32 : 16;
+    return p;
+}
+
 // Step 1, no HIP calls: the kernel row and the launch geometry of a search of nq queries for pools of K'
 template <int KL>
-int choose_scan(const mips_index* ix, int64_t nq, ScanPlan& pl) {
+int choose_scan(const mips_index* ix, const SearchCall& c, int64_t nq, ScanPlan& pl) {
     // variant 3 (query-stationary, LDS-DMA): the whole K of a wave's 32 queries lives in its VGPRs, so it
     // exists for a few row lengths only: 256 / 512 / 768 (8 waves, 2 per SIMD) and 1024 (4 waves, 1 per SIMD)
     int variant = ix->opt_variant;
-    // scan_kernel_v4 (16x16x32 MFMA shape, 4 sub-lists of 6): row pitch 384 .. 768 (at 256 the shorter chain no
-    // longer pays: 2.03 vs 2.00 ms), k <= 5, bf16 storage.  It is the default
+    // scan_kernel_v4 (16x16x32 MFMA shape, 4 sub-lists of 6): row pitch 384 .. 768, k <= 5, bf16 storage.  It is the default
     // there when more than one query tile shares the document stream (the MFMA-bound regime, where the shape's
     // higher clock pays: 4.54 vs 4.78 ms at BASELINE config 2); single-tile searches are HBM-bound and keep
-    // scan_kernel_v3's non-temporal document DMA.  "variant" = 3 / 4 forces one of the two.
-    const bool v4_opt = ix->optimistic && ix->rescan_depth == 0 && (KL == 16 || KL == 32) && ix->opt_variant == 0 &&
-                        ix->ld % 128 == 0 && ix->ld >= 384 && ix->ld <= 768 && ix->esize == 2 && ix->plane == 0;
-    const bool v4_shape = ix->ld % 128 == 0 && ix->ld >= 384 && ix->ld <= 768 && (KL == 8 || v4_opt) && ix->esize == 2 && ix->plane == 0;
+    // scan_kernel_v3's non-temporal document DMA.  "variant" = 3 / 4 forces one of the two.  Optimistic pools (K' = 16 / 32,
+    // pool_policy) come from it as well
+    const bool v4_opt = c.optimistic && c.ld != 1024;
+    const bool v4_shape = v4_pitch(c.ld) && (KL == 8 || v4_opt) && ix->esize == 2 && c.plane == 0;
     const bool v4_forced = variant == 4 && v4_shape;
     const bool v4_auto = variant == 0 && v4_shape;
     if (variant != 1 && variant != 3) variant = 3; // (4 was decided above; the rest of the function only knows 1 and 3)
-    const bool v3_dim = (ix->ld % 128 == 0 && ix->ld <= 768) || ix->ld == 1024;
-    const bool v3_long = ix->ld == 256 || ix->ld == 512 || ix->ld == 768 || ix->ld == 1024; // pitches with K' = 16 / 32 instances
+    const bool v3_dim = (c.ld % 128 == 0 && c.ld <= 768) || c.ld == 1024;
+    const bool v3_long = c.ld == 256 || c.ld == 512 || c.ld == 768 || c.ld == 1024; // pitches with K' = 16 / 32 instances
     constexpr bool kl_short = KL <= 10; // K' = 8 / 10 lists fit the 8-wave (two per SIMD) configuration
     const bool f8 = ix->esize == 1; // e4m3 index: scan_kernel_f8 only (row lengths 256..1024, K' <= 16)
-    const bool f32x = ix->plane > 0; // fp32-exact mode: generic kernel over the [hi | lo] planes, three k segments
+    const bool f32x = c.plane > 0; // fp32-exact mode: generic kernel over the [hi | lo] planes, three k segments
     // e4m3 documents x bf16 queries (MIPS_DTYPE_FP8_E4M3_DOCS): scan_kernel_e8, tiles of 32 queries (up to 32 queries, and at
     // row pitch 1024) or 64; pools of 8 / 10 / 16 / 32 out of 8 sub-lists of 6 per (query, split), the class words vouching for
     // 8 PUB documents
     const bool e8 = ix->mixed;
     if (e8) {
-        if (ix->ld % 256 != 0 || ix->ld > 1024) return fail(MIPS_E_UNSUPPORTED, "e4m3-documents index: d must pad to 256/512/768/1024");
+        if (c.ld % 256 != 0 || c.ld > 1024) return fail(MIPS_E_UNSUPPORTED, "e4m3-documents index: d must pad to 256/512/768/1024");
         variant = 3;
     } else if (f8) {
-        if (ix->ld % 256 != 0 || ix->ld > 1024 || KL > 16) return fail(MIPS_E_UNSUPPORTED, "fp8 index: d must pad to 256/512/768/1024 and k <= 13");
+        if (c.ld % 256 != 0 || c.ld > 1024 || KL > 16) return fail(MIPS_E_UNSUPPORTED, "fp8 index: d must pad to 256/512/768/1024 and k <= 13");
         variant = 3;
     } else if (f32x || !v3_dim || (!kl_short && !v3_long && !v4_opt)) {
         variant = 1; // no query-stationary configuration: generic tiles
@@ -190,10 +259,10 @@ int choose_scan(const mips_index* ix, int64_t nq, ScanPlan& pl) {
     // K' = 8 / 10 (k <= 7) at d <= 768: 8 waves, two per SIMD (256 registers each, no spill up to K' = 10).
     // Longer lists or d = 1024 do not fit next to the fragments there: 4 waves, one per SIMD, 512 registers,
     // 128 queries per workgroup.
-    const int v3_waves = (!f8 && !v4_opt && (ix->ld == 1024 || !kl_short)) ? 4 : 8;
+    const int v3_waves = (!f8 && !v4_opt && (c.ld == 1024 || !kl_short)) ? 4 : 8;
     // fp8: scan_kernel_f8x (16x16x128 MFMA shape, 64-document blocks, 4 sub-lists of 6) for k <= 5 and row pitches
     // up to 768 bytes; scan_kernel_f8 (32x32x64, 32-document blocks) otherwise or when "variant" = 3 asks for it
-    const bool want_f8x = f8 && !e8 && KL == 8 && ix->ld <= 768 && ix->opt_variant != 3;
+    const bool want_f8x = f8 && !e8 && KL == 8 && c.ld <= 768 && ix->opt_variant != 3;
     // scan_kernel_k3: row pitch 1024, K split over wave pairs of 48 queries each -- 192 stationary queries per CU, a third less
     // L2 -> LDS fill per flop than the 128-query configuration of scan_kernel_v3, which is what bounds pitch 1024 (measured
     // 30.6 vs 31.3 ms at 2^22 x 1024 for a pair kernel with 128 queries: profiles/r2_pitch1024 -- both sat on that fill).
@@ -203,9 +272,8 @@ int choose_scan(const mips_index* ix, int64_t nq, ScanPlan& pl) {
     // "optimistic" pools of scan_kernel_v4 at this pitch: first stage of the fp32-exact search at d in (768, 1024], bf16 searches
     // with 8 <= k <= 29, and k <= 5 on large indexes, where the MFMA error bound at K = 1024 reaches the 8th best score of one
     // query in a few thousand and a flagged query costs a pass over the index)
-    const bool k3_opt = ix->optimistic && ix->rescan_depth == 0 && (KL == 16 || KL == 32) && ix->opt_variant == 0 &&
-                        ix->ld == 1024 && ix->esize == 2 && ix->plane == 0 && !ix->mixed && nq > 256;
-    const bool k3_shape = ix->ld == 1024 && (KL == 8 || k3_opt) && ix->esize == 2 && ix->plane == 0;
+    const bool k3_opt = c.optimistic && c.ld == 1024;
+    const bool k3_shape = c.ld == 1024 && (KL == 8 || k3_opt) && ix->esize == 2 && c.plane == 0;
     const bool want_k3 = k3_opt || (k3_shape && (ix->opt_variant == 7 || (ix->opt_variant == 0 && nq > 256)));
     constexpr int K3_KLL = 4; // entries per sub-list (the third accumulator set is paid for with shorter lists)
     // (a variant on 16-document stages -- 4-stage ring, three blocks in flight, one barrier per 16 documents -- was built and
@@ -228,28 +296,28 @@ int choose_scan(const mips_index* ix, int64_t nq, ScanPlan& pl) {
     const ScanInstance* rows = nullptr;
     if (e8) { // pools of 8 PUB: K' = 8 / 10, 16 / 32
         rows = e8_instances(&nrow);
-        pl.row = find_instance(rows, nrow, ix->ld, nt, KL <= 8 ? 1 : KL <= 16 ? 2 : 4, e8_ncb(nq));
+        pl.row = find_instance(rows, nrow, c.ld, nt, KL <= 8 ? 1 : KL <= 16 ? 2 : 4, e8_ncb(nq));
     } else if (want_k3) { // pool of 8 PUB candidates: every sub-list vouches for its PUB-th best
         rows = k3_instances(&nrow);
-        pl.row = find_instance(rows, nrow, ix->ld, false, KL / 8);
+        pl.row = find_instance(rows, nrow, c.ld, false, KL / 8);
     } else if (want_v4) { // pools of 8 (PUB 1) or, optimistic, of 16 / 32: every sub-list vouches for its 4th best (8 x 4 = 32 documents)
         rows = v4_instances(&nrow);
-        pl.row = find_instance(rows, nrow, ix->ld, nt, v4_opt ? 4 : 1);
+        pl.row = find_instance(rows, nrow, c.ld, nt, v4_opt ? 4 : 1);
     } else if (want_f8x) {
         rows = f8x_instances(&nrow);
-        pl.row = find_instance(rows, nrow, ix->ld, nt);
+        pl.row = find_instance(rows, nrow, c.ld, nt);
     } else if (f8) {
         rows = f8_instances<KL>(&nrow);
-        pl.row = find_instance(rows, nrow, ix->ld, nt);
+        pl.row = find_instance(rows, nrow, c.ld, nt);
     } else if (variant == 1) {
         pl.row = generic_instance<KL>();
     } else {
         // K' = 8 / 10; true K' = 16 / 32 lists: pitches 256 / 512 / 768 and (round 3) 1024 -- k = 8 .. 29 and stage 1 of the
         // two-stage fp32 search at Longformer-large width no longer fall back to the generic kernel there
         rows = v3_instances<KL>(&nrow);
-        pl.row = find_instance(rows, nrow, ix->ld, nt);
+        pl.row = find_instance(rows, nrow, c.ld, nt);
     }
-    if (pl.row == nullptr) return fail(MIPS_E_UNSUPPORTED, "no scan-kernel instance for row pitch %d, K' = %d", ix->ld, KL);
+    if (pl.row == nullptr) return fail(MIPS_E_UNSUPPORTED, "no scan-kernel instance for row pitch %d, K' = %d", c.ld, KL);
     pl.stationary = variant == 3;
     pl.f32x = f32x;
     pl.tn = tn;
@@ -266,8 +334,8 @@ int choose_scan(const mips_index* ix, int64_t nq, ScanPlan& pl) {
     // "rounds" of wg_target resident workgroups: among the multiples of 8 up to 64 take the one whose last
     // round is fullest (ties: fewer splits = longer streams, fewer lists to merge).
     int nsplit;
-    if (ix->opt_nsplit > 0) {
-        nsplit = (int)round_up(ix->opt_nsplit, 8);
+    if (c.nsplit > 0) {
+        nsplit = (int)round_up(c.nsplit, 8);
     } else {
         nsplit = (int)round_up(std::max(1, (wg_target + nqt - 1) / nqt), 8);
         double best = -1.0;
@@ -304,29 +372,30 @@ int choose_scan(const mips_index* ix, int64_t nq, ScanPlan& pl) {
 }
 
 // Step 2: the ONE place that launches a scan kernel.  `a`: the common arguments; the e4m3 families wrap them
-inline int launch_scan(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs& a, int name_arg, hipStream_t st) {
+inline int launch_scan(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const mips::ScanArgs& a, int name_arg, hipStream_t st) {
     const ScanInstance& e = *pl.row;
     mips::ScanArgsF8 f8a;
     mips::ScanArgsE8 e8a;
     const void* arg = &a;
     if (e.args == ScanArgKind::F8) {
-        f8a.docs = ix->rows;
-        f8a.qbuf = (const uint8_t*)ix->qbuf.p;
+        f8a.docs = c.rows;
+        f8a.qbuf = (const uint8_t*)c.qbuf;
         f8a.c = a;
         arg = &f8a;
     } else if (e.args == ScanArgKind::E8) {
-        e8a.docs = ix->rows;
+        e8a.docs = c.rows;
         e8a.c = a;
         arg = &e8a;
     }
     const int slot = ix->ev_next;
+    const bool timed = c.timed && ix->timing_armed; // (the bench's event window times the first scan of a search only)
     HIP_TRY(hipFuncSetAttribute(e.fn, hipFuncAttributeMaxDynamicSharedMemorySize, e.lds));
-    if (ix->timing_armed) HIP_TRY(hipEventRecord(ix->ev0[slot], st));
+    if (timed) HIP_TRY(hipEventRecord(ix->ev0[slot], st));
     void* kargs[] = {const_cast<void*>(arg)};
     HIP_TRY(hipLaunchKernel(e.fn, dim3((unsigned)pl.grid), dim3((unsigned)e.threads), kargs, (size_t)e.lds, st));
-    set_kernel_name(ix, e.name, name_arg);
+    if (c.timed) set_kernel_name(ix, e.name, name_arg);
     HIP_TRY(hipGetLastError());
-    if (ix->timing_armed) {
+    if (timed) {
         HIP_TRY(hipEventRecord(ix->ev1[slot], st));
         ix->ev_next = (slot + 1) % mips_index::kEvRing;
         if (++ix->ev_count == mips_index::kEvRing) ix->timing_armed = false; // window full
@@ -337,7 +406,7 @@ inline int launch_scan(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs&
 // Step 3: the tail behind the scan -- (1) K' best candidates per query by MFMA score, (2) lane-packed exact re-score + final
 // order, with the margin check's buffers.  tail_st: stream of the two launches when `split` (else the scan's own)
 template <int KL>
-int launch_tail(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs& a, int64_t nq, int k, float* d_out_s, int64_t* d_out_i,
+int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const mips::ScanArgs& a, int64_t nq, int k, float* d_out_s, int64_t* d_out_i,
                 int64_t* d_out_packed, int64_t idx_offset, hipStream_t st, hipStream_t tail_st, bool split) {
     const bool f32x = pl.f32x, e8 = ix->mixed, f8 = ix->esize == 1;
     int rc;
@@ -345,12 +414,12 @@ int launch_tail(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs& a, int
     m.part_s = a.part_s;
     m.part_i = a.part_i;
     m.ncand = (int)pl.ncand;
-    const bool f32r = f32x || ix->fast_f32; // exact re-score on the fp32 rows (stage 1 of the two-stage search included)
-    m.docs = f32r ? (const void*)ix->rows_f32 : (const void*)ix->rows;
-    m.qbuf = f32r ? (const void*)ix->qf32.p : (const void*)a.qbuf;
-    m.ld = ix->fast_f32 ? ix->plane_keep : f32x ? ix->plane : ix->ld;
+    const bool f32r = f32x || c.stage1; // exact re-score on the fp32 rows (stage 1 of the two-stage search included)
+    m.docs = f32r ? (const void*)ix->rows_f32 : (const void*)c.rows;
+    m.qbuf = f32r ? c.qf32 : (const void*)a.qbuf;
+    m.ld = c.stage1 ? c.rescore_ld : f32x ? c.plane : c.ld;
     m.k = k;
-    m.metric = ix->call_metric;
+    m.metric = c.metric;
     m.phi = ix->phi;
     m.idx_offset = idx_offset;
     m.out_s = d_out_s;
@@ -369,13 +438,13 @@ int launch_tail(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs& a, int
     // sum |q_j x_j| <= d 2^-23 |q| |x| (u = 2^-23 allows truncating adders).  fp32-exact mode scans hi.qhi + hi.qlo +
     // lo.qhi of bf16 splits: the dropped lo.qlo term adds 2^-16 |q| |x|, and there are three times the terms.
     m.err_c = f32x ? (3.0 * (double)ix->d * 1.1920928955078125e-07 + 1.52587890625e-05) : (double)ix->d * 1.1920928955078125e-07;
-    m.nq_dev = ix->nq_dev;
-    if (ix->fast_f32) { // the scan's operands are bf16(q), bf16(x): norms within 2^-8 of |q|, |x|
+    m.nq_dev = c.nq_dev;
+    if (c.stage1) { // the scan's operands are bf16(q), bf16(x): norms within 2^-8 of |q|, |x|
         m.err_c *= 1.01;
         m.dres2 = ix->dres2_dev;
         m.qerr2 = (const double*)ix->qerr2.p;
     }
-    if (ix->opt_margin != 0) {
+    if (c.margin != 0) {
         rc = ix->mbnd.ensure((size_t)nq * sizeof(float));
         if (rc) return rc;
         rc = ix->mflag.ensure((size_t)nq);
@@ -387,7 +456,7 @@ int launch_tail(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs& a, int
         m.flag = (unsigned char*)ix->mflag.p;
         m.nflag = (unsigned*)ix->gthr.p + (size_t)pl.nq_pad * 8 + 1; // zeroed with the insert bounds by the query staging
         ix->last_nflag_dev = m.nflag;
-        if (ix->rescan_depth == 0) { // what the exact resolution of flagged queries starts from (resolve_kernels.hpp)
+        if (!c.rescan) { // what the exact resolution of flagged queries starts from (resolve_kernels.hpp)
             rc = ix->keyk.ensure((size_t)nq * sizeof(float));
             if (rc) return rc;
             rc = ix->qqv.ensure((size_t)nq * sizeof(double));
@@ -408,7 +477,7 @@ int launch_tail(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs& a, int
     }
     mips::merge_select_kernel<KL><<<(int)nq, 64, 0, st>>>(m, cand);
     HIP_TRY(hipGetLastError());
-    const bool l2 = ix->call_metric == MIPS_METRIC_L2;
+    const bool l2 = c.metric == MIPS_METRIC_L2;
     const int rgrid = (int)((nq + (64 / KL) - 1) / (64 / KL));
     if (f32r && l2) mips::rescore_rank_kernel<KL, mips::ElemF32, true><<<rgrid, 64, 0, st>>>(m, cand, nq);
     else if (f32r) mips::rescore_rank_kernel<KL, mips::ElemF32, false><<<rgrid, 64, 0, st>>>(m, cand, nq);
@@ -428,10 +497,10 @@ int launch_tail(mips_index* ix, const ScanPlan& pl, const mips::ScanArgs& a, int
 
 // tail_st: stream of the select + exact re-score launches (nullptr or == st: the scan's own stream)
 template <int KL>
-int launch_search(mips_index* ix, int64_t nq, int k, float* d_out_s, int64_t* d_out_i, int64_t* d_out_packed,
+int launch_search(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_out_s, int64_t* d_out_i, int64_t* d_out_packed,
                   int64_t idx_offset, hipStream_t st, hipStream_t tail_st = nullptr, bool split = false) {
     ScanPlan pl;
-    int rc = choose_scan<KL>(ix, nq, pl);
+    int rc = choose_scan<KL>(ix, c, nq, pl);
     if (rc) return rc;
     rc = ix->part_s.ensure((size_t)pl.nq_pad * pl.ncand * sizeof(float));
     if (rc) return rc;
@@ -439,18 +508,18 @@ int launch_search(mips_index* ix, int64_t nq, int k, float* d_out_s, int64_t* d_
     if (rc) return rc;
 
     mips::ScanArgs a;
-    a.docs = (const uint16_t*)ix->rows;
-    a.qbuf = (const uint16_t*)ix->qbuf.p;
+    a.docs = (const uint16_t*)c.rows;
+    a.qbuf = (const uint16_t*)c.qbuf;
     a.ntotal = ix->ntotal;
-    a.ld = ix->ld;
-    a.ksteps = pl.f32x ? 3 * ix->plane / mips::BK : ix->ld / mips::BK;
-    a.plane = ix->plane;
+    a.ld = c.ld;
+    a.ksteps = pl.f32x ? 3 * c.plane / mips::BK : c.ld / mips::BK;
+    a.plane = c.plane;
     a.ntiles = pl.ntiles;
     a.tiles_per_split = pl.tps;
     a.nsplit = pl.nsplit;
     a.nqt = pl.nqt;
     a.nq = (int)nq;
-    a.nq_dev = ix->nq_dev;
+    a.nq_dev = c.nq_dev;
     a.qgroups = pl.qgroups;
     a.qt_per_group = pl.qt_per_group;
     a.splits_per_group = pl.nsplit / (8 / pl.qgroups);
@@ -459,18 +528,16 @@ int launch_search(mips_index* ix, int64_t nq, int k, float* d_out_s, int64_t* d_
     a.gthr = nullptr;
     a.err = nullptr;
     a.spin_limit = ix->opt_spin_limit != 0 ? ix->opt_spin_limit : (1 << 22);
-    ix->err_off = 0;
     if (pl.stationary) {
         // shared insert bounds: 8 class words per query (2 lane-half words in the older layouts) + error word
         const size_t thr_words = (size_t)pl.nq_pad * 8;
         // (allocated and cleared by mips_search together with the query staging)
         a.gthr = (unsigned*)ix->gthr.p;
         a.err = a.gthr + thr_words;
-        ix->err_off = thr_words;
     }
-    rc = launch_scan(ix, pl, a, KL, st);
+    rc = launch_scan(ix, c, pl, a, KL, st);
     if (rc) return rc;
-    return launch_tail<KL>(ix, pl, a, nq, k, d_out_s, d_out_i, d_out_packed, idx_offset, st, tail_st, split);
+    return launch_tail<KL>(ix, c, pl, a, nq, k, d_out_s, d_out_i, d_out_packed, idx_offset, st, tail_st, split);
 }
 
 #undef MIPS_TABLE_END

@@ -9,12 +9,12 @@ static_assert(kWideSlice == 4 * mips::RANGE_LIMS_THREADS, "range_lims_kernel tak
 
 // d_lims [nq + 1], d_s / d_i [cap] are DEVICE buffers; radii is the caller's HOST array.  nq > 0 and ntotal > 0.
 int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* d_lims, float* d_s, int64_t* d_i, int64_t cap,
-                 int64_t idx_offset, bool q_dev, Selector sel, hipStream_t st) {
+                 int64_t idx_offset, bool q_dev, Selector sel, int metric, hipStream_t st) {
     // a filtered or grouped search: only the scan changes, the filter sees appended rows alone
     const bool grouped = sel.qlab != nullptr;
     const bool masked = sel.bits != nullptr && !grouped;
     const bool f32x = ix->plane > 0;
-    const bool l2 = ix->call_metric == MIPS_METRIC_L2;
+    const bool l2 = metric == MIPS_METRIC_L2;
     const int sld = f32x ? ix->hp : ix->ld;    // row pitch of the scanned bf16 rows
     const int cld = f32x ? ix->plane : ix->ld; // row pitch of the canonical rows and queries
     int rc;

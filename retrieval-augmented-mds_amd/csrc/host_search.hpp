@@ -1,6 +1,8 @@
 // Host side of libmips_hip.so, part 3 of 3 (included by mips_hip.hip): what a search does around its scan -- the one-launch
-// kernel for the reference's own call shape, the exact pass of flagged queries (resolve_flagged), the fall-back re-scans, the
-// certificate (finish_margin), the optimistic / two-stage first scans (scan_and_finish) and the scope of the margin mode.
+// kernel for the reference's own call shape, the exact pass of flagged queries (resolve_flagged), the ONE re-scan of flagged
+// queries (rescan_flagged) behind its stream-ordered and its synchronising caller, the certificate (finish_margin) and the
+// optimistic / two-stage first scans (scan_and_finish).  A nested launch -- stage 1, a re-scan -- is a modified COPY of the
+// SearchCall; the index is not touched to describe it.
 #pragma once
 
 namespace {
@@ -13,7 +15,7 @@ constexpr int64_t kTinyMaxRows = 1 << 16;
 // admissible because of the certificate alone
 bool tiny_eligible(const mips_index* ix, int64_t nq, int k_fetch, bool certifies) {
     if (!(ix->opt_tiny != 0 && nq >= 1 && nq <= 16 && k_fetch <= mips::TINY_MAXK && ix->ntotal > 0 && ix->ntotal <= kTinyMaxRows &&
-          ix->esize == 2 && ix->rescan_depth == 0))
+          ix->esize == 2))
         return false;
     if (ix->plane > 0) return certifies && ix->opt_f32_fast != 0 && ix->hp > 0 && ix->hp <= 1024 && ix->hp % 128 == 0;
     return ix->ld <= 1024 && ix->ld % 128 == 0;
@@ -34,8 +36,8 @@ int ensure_resolve_buffers(mips_index* ix, int64_t nq) {
 }
 
 // handoff: prepare the stream-ordered exact pass (resolve_flagged with skip_compact) -- the kernel's last workgroup writes
-// the flag list, clears the hit counters and copies the staged queries out when something was flagged
-int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int k_fetch, int k_out, int normalize, const int64_t* ignore_dev,
+// the flag list, clears the hit counters and copies the staged queries out when something was flagged (c.qbuf / c.qf32: where to)
+int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, int64_t nq, int k_fetch, int k_out, int normalize, const int64_t* ignore_dev,
                 float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool handoff) {
     const bool f32x = ix->plane > 0;
     const int tld = f32x ? ix->hp : ix->ld; // row pitch of the scanned bf16 rows
@@ -91,7 +93,7 @@ int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int 
     m.qbuf = nullptr;
     m.ld = tld;
     m.k = k_fetch;
-    m.metric = ix->call_metric;
+    m.metric = c.metric;
     m.phi = ix->phi;
     m.idx_offset = idx_offset;
     m.out_s = nullptr;
@@ -111,7 +113,7 @@ int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int 
     ix->last_unresolved = 0;
     ix->last_nflag_dev = nullptr;
     ix->first_nflag_dev = nullptr;
-    if (ix->opt_margin != 0) {
+    if (c.margin != 0) {
         rc = ix->mbnd.ensure(16 * sizeof(float));
         if (rc) return rc;
         rc = ix->mflag.ensure(16);
@@ -134,6 +136,8 @@ int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int 
             a.res_unres = (unsigned*)(a.res_ids + nq + 1);
             a.res_hit_n = (int*)ix->hit_n.p;
             a.q_out = f32x ? ix->qf32.p : ix->qbuf.p;
+            if (f32x) c.qf32 = a.q_out; // (the exact pass reads the flagged queries from there)
+            else c.qbuf = a.q_out;
             m.keyk = (float*)ix->keyk.p;
             m.qq_out = (double*)ix->qqv.p;
         }
@@ -146,7 +150,7 @@ int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int 
         kern<<<nwg, mips::TINY_THREADS, lds, st>>>(a);
         return MIPS_OK;
     };
-    const bool l2m = ix->call_metric == MIPS_METRIC_L2;
+    const bool l2m = c.metric == MIPS_METRIC_L2;
     if (f32x) rc = l2m ? go(mips::tiny_search_kernel<true, true>) : go(mips::tiny_search_kernel<false, true>);
     else rc = l2m ? go(mips::tiny_search_kernel<true, false>) : go(mips::tiny_search_kernel<false, false>);
     if (rc) return rc;
@@ -163,7 +167,7 @@ int tiny_search(mips_index* ix, const void* q_dev, int q_dtype, int64_t nq, int 
 constexpr int kUseRescan = 1;
 // skip_compact: the flag list, its count and the cleared counters are already on the device (the one-launch kernel's hand-off).
 // ignore / k_out: the fused hook call's ignore filter (ResolveArgs), d_s / d_i then are [nq][k_out].
-int resolve_flagged(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool certify_now,
+int resolve_flagged(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool certify_now,
                     bool skip_compact = false, const int64_t* ignore = nullptr, int k_out = 0) {
     if (k > mips::RESOLVE_OVF_K) return fail(MIPS_E_UNSUPPORTED, "resolve_flagged: k = %d exceeds RESOLVE_OVF_K", k);
     int rc = ensure_resolve_buffers(ix, nq); // (never reallocates behind a hand-off: same sizes as tiny_search asked for)
@@ -188,7 +192,7 @@ int resolve_flagged(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i,
     mips::ResolveArgs a;
     const bool f32x = ix->plane > 0;
     a.rows = f32x ? (const void*)ix->rows_f32 : (const void*)ix->rows;
-    a.y = f32x ? (const void*)ix->qf32.p : (const void*)ix->qbuf.p;
+    a.y = f32x ? c.qf32 : c.qbuf;
     a.ld = f32x ? ix->plane : ix->ld;
     a.ntotal = ix->ntotal;
     a.ids = ids;
@@ -213,7 +217,7 @@ int resolve_flagged(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i,
     int lds = mips::RESOLVE_QB * a.ld * (int)sizeof(double) + mips::RESOLVE_WAVES * 64 * 9 * 16;
     const int rows_per_wg = 64 * mips::RESOLVE_WAVES;
     int grid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (ix->ntotal + rows_per_wg - 1) / rows_per_wg));
-    const bool l2 = ix->call_metric == MIPS_METRIC_L2;
+    const bool l2 = c.metric == MIPS_METRIC_L2;
     auto go = [&](auto kern) -> int {
         HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         kern<<<grid, 64 * mips::RESOLVE_WAVES, lds, st>>>(a);
@@ -276,80 +280,92 @@ int resolve_flagged(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i,
     return MIPS_OK;
 }
 
-// "margin_check" = 3, device outputs: the re-scan of finish_margin without its two synchronisations.  The flags of the first
-// scan are compacted into a list + count ON THE DEVICE; the staged rows of the flagged queries are gathered; the second scan
-// (widest lists) is launched for ALL nq queries' worth of workgroups, which read the count and leave when they are past it
-// (ScanArgs::nq_dev); select, re-score and the scatter over the first results do the same.  With nothing flagged this costs
-// a handful of empty launches (tens of microseconds); mips_index_margin_stats reads both counters when asked.
-// gate_above >= 0: the fall-back behind the exact pass for searches whose FIRST scan was an optimistic one (two-stage fp32 search,
-// pools of 32 out of sub-lists): the exact pass leaves a search that flagged more than gate_above queries alone, and first results
-// selected by bf16 scores / short sub-lists must not stand uncertified -- so this re-scan runs exactly then (its launches are
-// sized by a count that is 0 otherwise) and its own still-flagged count replaces the exact pass's "unresolved".
+// Widest lists this storage type has (K' = 32; 16 on an fp8 index), or 0 when the first scan already kept them.  recheck: the
+// first scan was stage 1 of the two-stage fp32 search or took its pool from sub-lists (PoolPolicy::recheck) -- the second is
+// the three-segment scan / true K' = 32 lists whatever K' was
 template <int KL>
-int rescan_on_stream(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool fast_first,
-                     int gate_above = -1) {
-    const bool f8 = ix->esize == 1;
-    const int wide = f8 ? (KL < 16 ? 16 : 0) : (KL < 32 || fast_first ? 32 : 0);
+int widest_lists(const mips_index* ix, bool recheck) {
+    return ix->esize == 1 ? (KL < 16 ? 16 : 0) : (KL < 32 || recheck ? 32 : 0);
+}
+
+// The second scan of flagged queries, both forms: the staged rows of the queries listed in ids (device) are gathered into a
+// compact query buffer, the insert bounds cleared, the compact queries searched with the widest lists -- a nested launch that
+// is neither timed nor named and prepares nothing for a third scan -- and its rows scattered over the first results.
+//   synchronising form:  n = the flagged count as the host read it, cnt = nullptr
+//   stream-ordered form: n = ALL queries (what the launches are sized for), cnt = the count on the device: workgroups past it
+//                        leave (ScanArgs::nq_dev), select, re-score and the scatter do the same
+// nsplit: few flagged queries = few query tiles, so each tile's scan is spread over more splits than the automatic choice makes
+// (0 = that choice; the caller's heuristic, which "nsplit" overrides)
+int rescan_flagged(mips_index* ix, const SearchCall& c, int wide, const int* ids, int64_t n, const int* cnt, int nsplit, int k, float* d_s,
+                   int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st) {
+    const int64_t n_pad = query_pad(ix, n);
+    const size_t row_bytes = (size_t)c.ld * ix->qsize;
+    int rc = ix->qbuf2.ensure((size_t)n_pad * row_bytes);
+    if (rc) return rc;
+    rc = ix->tmp_s.ensure((size_t)n * k * sizeof(float));
+    if (rc) return rc;
+    rc = ix->tmp_i.ensure((size_t)n * k * sizeof(int64_t) * 2);
+    if (rc) return rc;
+    SearchCall r = c;
+    r.qbuf = ix->qbuf2.p;
+    mips::gather_rows_kernel<<<grid_for(n_pad * (int64_t)(row_bytes / 16), 256), 256, 0, st>>>((const unsigned char*)c.qbuf, ids, n, n_pad, (int)row_bytes,
+                                                                                              (unsigned char*)ix->qbuf2.p, cnt);
+    if (c.plane > 0) {
+        const size_t rb32 = (size_t)c.plane * sizeof(float);
+        rc = ix->qf32b.ensure((size_t)n_pad * rb32);
+        if (rc) return rc;
+        r.qf32 = ix->qf32b.p;
+        mips::gather_rows_kernel<<<grid_for(n_pad * (int64_t)(rb32 / 16), 256), 256, 0, st>>>((const unsigned char*)c.qf32, ids, n, n_pad, (int)rb32,
+                                                                                            (unsigned char*)ix->qf32b.p, cnt);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(ix->gthr.p, 0, (size_t)(n_pad * 8 + 4) * sizeof(unsigned), st)); // insert bounds, error word, flag counter
+    r.optimistic = false;
+    r.rescan = true;
+    r.nq_dev = cnt;
+    r.nsplit = c.nsplit != 0 ? c.nsplit : nsplit;
+    r.timed = false; // the bench's event window times the first scan only, and last_kernel keeps naming it
+    float* ts = (float*)ix->tmp_s.p;
+    int64_t* ti = (int64_t*)ix->tmp_i.p;
+    if (wide == 32) rc = launch_search<32>(ix, r, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st);
+    else rc = launch_search<16>(ix, r, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st);
+    if (rc) return rc;
+    if (packed) {
+        mips::scatter_i64_kernel<<<grid_for(n * 2 * k, 256), 256, 0, st>>>(ti, ids, n, 2 * k, d_i, cnt);
+    } else {
+        mips::scatter_i64_kernel<<<grid_for(n * k, 256), 256, 0, st>>>(ti, ids, n, k, d_i, cnt);
+        mips::scatter_f32_kernel<<<grid_for(n * k, 256), 256, 0, st>>>(ts, ids, n, k, d_s, cnt);
+    }
+    HIP_TRY(hipGetLastError());
+    return MIPS_OK;
+}
+
+// "margin_check" = 3, device outputs: the re-scan without a synchronisation.  The flags of the first scan are compacted into a
+// list + count ON THE DEVICE and rescan_flagged runs in its stream-ordered form.  With nothing flagged this costs a handful of
+// empty launches (tens of microseconds); mips_index_margin_stats reads both counters when asked.
+// gate_above >= 0: the fall-back behind the exact pass for searches whose first scan was an optimistic one (PoolPolicy::recheck):
+// the exact pass leaves a search that flagged more than gate_above queries alone, and first results selected by bf16 scores /
+// short sub-lists must not stand uncertified -- so this re-scan runs exactly then (its launches are sized by a count that is 0
+// otherwise) and its own still-flagged count replaces the exact pass's "unresolved".
+template <int KL>
+int rescan_on_stream(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st,
+                     bool recheck, int gate_above = -1) {
+    const int wide = widest_lists<KL>(ix, recheck);
     if (gate_above < 0) {
         ix->last_flagged = -1; // (device only)
         ix->last_max_n = 0;
     }
     if (wide == 0) return MIPS_OK; // already on the widest lists: counted only
-    const int64_t n_pad = query_pad(ix, nq);
-    const size_t row_bytes = (size_t)ix->ld * ix->qsize;
     int rc = ix->ids.ensure((size_t)(nq + 4) * sizeof(int));
     if (rc) return rc;
     int* ids = (int*)ix->ids.p;
     int* cnt = ids + nq + (gate_above >= 0 ? 2 : 0); // (gated: the exact pass's own count and unresolved counter stay where they are)
     unsigned* const exact_unres = (unsigned*)(ids + nq + 1);
     const int* const first_keep = ix->first_nflag_dev;
-    rc = ix->qbuf2.ensure((size_t)n_pad * row_bytes);
-    if (rc) return rc;
-    rc = ix->tmp_s.ensure((size_t)nq * k * sizeof(float));
-    if (rc) return rc;
-    rc = ix->tmp_i.ensure((size_t)nq * k * sizeof(int64_t) * 2);
-    if (rc) return rc;
     mips::compact_flags_kernel<<<1, 256, 0, st>>>((const unsigned char*)ix->mflag.p, (int)nq, ids, cnt, nullptr, 0, nullptr, gate_above);
-    mips::gather_rows_kernel<<<grid_for(n_pad * (int64_t)(row_bytes / 16), 256), 256, 0, st>>>((const unsigned char*)ix->qbuf.p, ids, 0, n_pad, (int)row_bytes,
-                                                                                              (unsigned char*)ix->qbuf2.p, cnt);
-    if (ix->plane > 0) {
-        const size_t rb32 = (size_t)ix->plane * sizeof(float);
-        rc = ix->qf32b.ensure((size_t)n_pad * rb32);
-        if (rc) return rc;
-        mips::gather_rows_kernel<<<grid_for(n_pad * (int64_t)(rb32 / 16), 256), 256, 0, st>>>((const unsigned char*)ix->qf32.p, ids, 0, n_pad, (int)rb32,
-                                                                                            (unsigned char*)ix->qf32b.p, cnt);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(ix->gthr.p, 0, (size_t)(n_pad * 8 + 4) * sizeof(unsigned), st)); // insert bounds, error word, flag counter
-    std::swap(ix->qbuf, ix->qbuf2);
-    std::swap(ix->qf32, ix->qf32b);
-    const bool armed = ix->timing_armed;
-    char name_keep[sizeof ix->last_kernel];
-    std::memcpy(name_keep, ix->last_kernel, sizeof name_keep);
-    ix->timing_armed = false;
-    ix->rescan_depth = 1;
-    ix->nq_dev = cnt;
-    const int ns_keep = ix->opt_nsplit;
-    if (ns_keep == 0 && nq <= 8192) ix->opt_nsplit = nq <= 4096 ? 128 : 64; // the flagged queries are few: spread each of their tiles over many CUs
-    float* ts = (float*)ix->tmp_s.p;
-    int64_t* ti = (int64_t*)ix->tmp_i.p;
-    if (wide == 32) rc = launch_search<32>(ix, nq, k, ts, ti, packed ? ti : nullptr, idx_offset, st, nullptr, false);
-    else rc = launch_search<16>(ix, nq, k, ts, ti, packed ? ti : nullptr, idx_offset, st, nullptr, false);
-    ix->opt_nsplit = ns_keep;
-    ix->nq_dev = nullptr;
-    ix->rescan_depth = 0;
-    ix->timing_armed = armed;
-    std::memcpy(ix->last_kernel, name_keep, sizeof name_keep);
-    std::swap(ix->qbuf, ix->qbuf2);
-    std::swap(ix->qf32, ix->qf32b);
+    // the flagged queries are few: spread each of their tiles over many CUs
+    rc = rescan_flagged(ix, c, wide, ids, nq, cnt, nq <= 4096 ? 128 : nq <= 8192 ? 64 : 0, k, d_s, d_i, packed, idx_offset, st);
     if (rc) return rc;
-    if (packed) {
-        mips::scatter_i64_kernel<<<grid_for(nq * 2 * k, 256), 256, 0, st>>>(ti, ids, 0, 2 * k, d_i, cnt);
-    } else {
-        mips::scatter_i64_kernel<<<grid_for(nq * k, 256), 256, 0, st>>>(ti, ids, 0, k, d_i, cnt);
-        mips::scatter_f32_kernel<<<grid_for(nq * k, 256), 256, 0, st>>>(ts, ids, 0, k, d_s, cnt);
-    }
-    HIP_TRY(hipGetLastError());
     if (gate_above >= 0) { // statistics stay the exact pass's; if this re-scan ran, what IT still flags is what is unresolved
         mips::adopt_rescan_count_kernel<<<1, 1, 0, st>>>(cnt, ix->last_nflag_dev, exact_unres);
         HIP_TRY(hipGetLastError());
@@ -363,32 +379,30 @@ int rescan_on_stream(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i
 }
 
 // Margin check, host side.  The re-score flagged every query whose k-th exact score is within the MFMA error bound of
-// what the candidate pool may have excluded (aux_kernels.hpp).  When the call may synchronise (host buffers, or
-// "margin_check" = 2) the flagged queries are re-scanned with the widest lists (K' = 32; 16 on an fp8 index): their
-// staged rows are gathered into a compact query buffer, searched again, and the rows scattered over the first
-// results.  Queries still flagged after that are counted as unresolved (mips_index_margin_stats).
+// what the candidate pool may have excluded (aux_kernels.hpp).  Flagged queries are settled exactly, by brute force on the
+// canonical scores (resolve_flagged: rows of up to 1024 columns); beyond that, with "resolve" = 0 and when more are flagged
+// than the exact pass takes, they are re-scanned with the widest lists -- on the stream ("margin_check" = 3, device outputs) or,
+// when the call may synchronise (host buffers, "margin_check" = 2), here: the flag list is read back and rescan_flagged runs in
+// its synchronising form.  Queries still flagged after that are counted as unresolved (mips_index_margin_stats).
 template <int KL>
-int finish_margin(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool out_dev,
-                  hipStream_t st, bool fast_first = false) {
+int finish_margin(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool out_dev,
+                  hipStream_t st, bool recheck) {
     ix->last_flagged = -1;
     ix->last_rescanned = 0;
     ix->last_unresolved = 0;
     ix->first_nflag_dev = nullptr;
-    if (ix->opt_margin == 0 || ix->rescan_depth != 0) return MIPS_OK;
-    if (out_dev && ix->opt_margin != 2 && ix->opt_margin != 3) return MIPS_OK; // counted on the device only
-    // flagged queries are settled exactly, by brute force on the canonical scores (rows of up to 1024 columns; beyond that
-    // -- and with "resolve" = 0 -- by the re-scan with the widest lists below)
-    if (ix->opt_resolve != 0 && (ix->plane > 0 ? ix->plane : ix->ld) <= 1024) {
-        const bool stream_ordered = out_dev && ix->opt_margin == 3;
-        const int r = resolve_flagged(ix, nq, k, d_s, d_i, packed, idx_offset, st, !stream_ordered);
-        if (r == MIPS_OK && stream_ordered && fast_first) {
+    if (!call_certifies(c.margin, out_dev)) return MIPS_OK; // off, or counted on the device only
+    const bool stream_ordered = out_dev && c.margin == 3;
+    if (ix->opt_resolve != 0 && (c.plane > 0 ? c.plane : c.ld) <= 1024) {
+        const int r = resolve_flagged(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, !stream_ordered);
+        if (r == MIPS_OK && stream_ordered && recheck) {
             const int max_n = ix->resolve_budget > 0 ? std::min(ix->resolve_budget, mips::RESOLVE_MAX) : mips::RESOLVE_MAX;
-            if (nq > max_n) return rescan_on_stream<KL>(ix, nq, k, d_s, d_i, packed, idx_offset, st, fast_first, max_n);
+            if (nq > max_n) return rescan_on_stream<KL>(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, recheck, max_n);
         }
         if (r != kUseRescan) return r;
         ix->first_nflag_dev = nullptr; // (more flagged than the exact pass takes: the tile re-scan below, which synchronises)
-    } else if (out_dev && ix->opt_margin == 3) {
-        return rescan_on_stream<KL>(ix, nq, k, d_s, d_i, packed, idx_offset, st, fast_first);
+    } else if (stream_ordered) {
+        return rescan_on_stream<KL>(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, recheck);
     }
     if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host, 64, hipHostMallocDefault));
     HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->last_nflag_dev, 4, hipMemcpyDeviceToHost, st));
@@ -396,10 +410,7 @@ int finish_margin(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, b
     const int64_t n = (int64_t)ix->nflag_host[0];
     ix->last_flagged = n;
     if (n == 0) return MIPS_OK;
-    constexpr int WIDE = 32;
-    const bool f8 = ix->esize == 1;
-    // (fast_first: the scan just done was stage 1 of the two-stage fp32 search -- the re-scan is the three-segment scan)
-    const int wide = f8 ? (KL < 16 ? 16 : 0) : (KL < WIDE || fast_first ? WIDE : 0);
+    const int wide = widest_lists<KL>(ix, recheck);
     if (wide == 0) { // already on the widest lists this storage type has
         ix->last_unresolved = n;
         return MIPS_OK;
@@ -408,64 +419,19 @@ int finish_margin(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, b
     std::string flags((size_t)nq, '\0');
     HIP_TRY(hipMemcpyAsync(&flags[0], ix->mflag.p, (size_t)nq, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    std::string idbuf((size_t)n * sizeof(int), '\0');
-    int* ids_h = reinterpret_cast<int*>(&idbuf[0]);
-    int64_t w = 0;
-    for (int64_t q = 0; q < nq && w < n; ++q)
-        if (flags[(size_t)q]) ids_h[w++] = (int)q;
-    if (w != n) return fail(MIPS_E_HIP, "margin check: flag count %lld does not match the flag array (%lld)", (long long)n, (long long)w);
+    std::vector<int> ids_h;
+    for (int64_t q = 0; q < nq && (int64_t)ids_h.size() < n; ++q)
+        if (flags[(size_t)q]) ids_h.push_back((int)q);
+    if ((int64_t)ids_h.size() != n)
+        return fail(MIPS_E_HIP, "margin check: flag count %lld does not match the flag array (%lld)", (long long)n, (long long)ids_h.size());
     int rc = ix->ids.ensure((size_t)n * sizeof(int));
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->ids.p, ids_h, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
-    const int* ids = (const int*)ix->ids.p;
-    const int64_t n_pad = query_pad(ix, n);
-    const size_t row_bytes = (size_t)ix->ld * ix->qsize;
-    rc = ix->qbuf2.ensure((size_t)n_pad * row_bytes);
+    HIP_TRY(hipMemcpyAsync(ix->ids.p, ids_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    // (the automatic split choice stops at 64; one 128-query tile of the three-segment scan on 64 workgroups took 17 ms at
+    // 2^20 x 768)
+    const int nsplit = n <= 1024 ? (int)std::max<int64_t>(64, std::min<int64_t>(256, round_up(512 / ((n + 127) / 128), 8))) : 0;
+    rc = rescan_flagged(ix, c, wide, (const int*)ix->ids.p, n, nullptr, nsplit, k, d_s, d_i, packed, idx_offset, st);
     if (rc) return rc;
-    mips::gather_rows_kernel<<<grid_for(n_pad * (int64_t)(row_bytes / 16), 256), 256, 0, st>>>((const unsigned char*)ix->qbuf.p, ids, n, n_pad,
-                                                                                              (int)row_bytes, (unsigned char*)ix->qbuf2.p);
-    if (ix->plane > 0) {
-        const size_t rb32 = (size_t)ix->plane * sizeof(float);
-        rc = ix->qf32b.ensure((size_t)n_pad * rb32);
-        if (rc) return rc;
-        mips::gather_rows_kernel<<<grid_for(n_pad * (int64_t)(rb32 / 16), 256), 256, 0, st>>>((const unsigned char*)ix->qf32.p, ids, n, n_pad, (int)rb32,
-                                                                                            (unsigned char*)ix->qf32b.p);
-    }
-    HIP_TRY(hipGetLastError());
-    rc = ix->tmp_s.ensure((size_t)n * k * sizeof(float));
-    if (rc) return rc;
-    rc = ix->tmp_i.ensure((size_t)n * k * sizeof(int64_t) * 2);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ix->gthr.p, 0, (size_t)(n_pad * 8 + 4) * sizeof(unsigned), st)); // insert bounds, error word, flag counter
-    std::swap(ix->qbuf, ix->qbuf2);
-    std::swap(ix->qf32, ix->qf32b);
-    const bool armed = ix->timing_armed;
-    char name_keep[sizeof ix->last_kernel];
-    std::memcpy(name_keep, ix->last_kernel, sizeof name_keep);
-    ix->timing_armed = false; // the bench's event window times the first scan only
-    ix->rescan_depth = 1;
-    // few flagged queries = few query tiles: spread each tile's scan over many more splits than the automatic choice makes
-    // (it stops at 64; one 128-query tile of the three-segment scan on 64 workgroups took 17 ms at 2^20 x 768)
-    const int ns_keep = ix->opt_nsplit;
-    if (ns_keep == 0 && n <= 1024) ix->opt_nsplit = (int)std::max<int64_t>(64, std::min<int64_t>(256, round_up(512 / ((n + 127) / 128), 8)));
-    float* ts = (float*)ix->tmp_s.p;
-    int64_t* ti = (int64_t*)ix->tmp_i.p;
-    if (wide == 32) rc = launch_search<32>(ix, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st);
-    else rc = launch_search<16>(ix, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st);
-    ix->opt_nsplit = ns_keep;
-    ix->rescan_depth = 0;
-    ix->timing_armed = armed;
-    std::memcpy(ix->last_kernel, name_keep, sizeof name_keep);
-    std::swap(ix->qbuf, ix->qbuf2);
-    std::swap(ix->qf32, ix->qf32b);
-    if (rc) return rc;
-    if (packed) {
-        mips::scatter_i64_kernel<<<grid_for(n * 2 * k, 256), 256, 0, st>>>(ti, ids, n, 2 * k, d_i);
-    } else {
-        mips::scatter_i64_kernel<<<grid_for(n * k, 256), 256, 0, st>>>(ti, ids, n, k, d_i);
-        mips::scatter_f32_kernel<<<grid_for(n * k, 256), 256, 0, st>>>(ts, ids, n, k, d_s);
-    }
-    HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->last_nflag_dev, 4, hipMemcpyDeviceToHost, st)); // still flagged on the widest lists
     HIP_TRY(hipStreamSynchronize(st));
     ix->last_rescanned = n;
@@ -473,66 +439,41 @@ int finish_margin(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, b
     return MIPS_OK;
 }
 
-// One scan + select + exact re-score + margin finish at list length KL.  fast: stage 1 of the two-stage search of an
-// fp32-exact index -- for the duration of the launch the index is viewed as the bf16 index rows_hi (pitch hp) with the
-// bf16 queries qhi; the re-score and the margin check still run on the fp32 rows (launch_search: fast_f32).  Queries the
-// widened margin cannot certify are re-scanned by finish_margin on the three-segment scan with K' = 32 lists.
+// One scan + select + exact re-score + margin finish at list length KL = pol.kl.  pol.fast: stage 1 of the two-stage search of an
+// fp32-exact index -- the launch gets a COPY of the call that views the index as the bf16 index rows_hi (pitch hp) with the bf16
+// queries qhi; the re-score and the margin check still run on the fp32 rows (SearchCall::stage1).  Queries the widened margin
+// cannot certify are settled by finish_margin, which sees the call as it came in.
 template <int KL>
-int scan_and_finish(mips_index* ix, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool out_dev, hipStream_t st,
-                    hipStream_t tail_st, bool split, bool fast, bool optimistic = false) {
-    int rc;
-    ix->optimistic = fast || optimistic;
-    if (fast) {
-        uint8_t* rows_keep = ix->rows;
-        const int ld_keep = ix->ld, plane_keep = ix->plane;
-        ix->rows = ix->rows_hi;
-        ix->ld = ix->hp;
-        ix->plane = 0;
-        ix->plane_keep = plane_keep;
-        ix->fast_f32 = true;
-        std::swap(ix->qbuf, ix->qhi);
-        rc = launch_search<KL>(ix, nq, k, d_s, d_i, packed ? d_i : nullptr, idx_offset, st, tail_st, split);
-        std::swap(ix->qbuf, ix->qhi);
-        ix->rows = rows_keep;
-        ix->ld = ld_keep;
-        ix->plane = plane_keep;
-        ix->fast_f32 = false;
-    } else {
-        rc = launch_search<KL>(ix, nq, k, d_s, d_i, packed ? d_i : nullptr, idx_offset, st, tail_st, split);
+int scan_and_finish(mips_index* ix, const SearchCall& c, const PoolPolicy& pol, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed,
+                    int64_t idx_offset, bool out_dev, hipStream_t st, hipStream_t tail_st, bool split) {
+    SearchCall first = c;
+    first.optimistic = pol.optimistic;
+    if (pol.fast) {
+        first.rows = ix->rows_hi;
+        first.ld = ix->hp;
+        first.plane = 0;
+        first.stage1 = true;
+        first.rescore_ld = c.plane;
+        first.qbuf = ix->qhi.p;
     }
-    const bool first_was_optimistic = ix->optimistic;
-    ix->optimistic = false;
+    int rc = launch_search<KL>(ix, first, nq, k, d_s, d_i, packed ? d_i : nullptr, idx_offset, st, tail_st, split);
     if (rc) return rc;
     if (split) { // scan on st, tail on tail_st: the certificate, when asked for, is part of the tail
         ix->last_flagged = -1;
         ix->first_nflag_dev = nullptr;
-        if (ix->opt_margin == 3 && out_dev && ix->opt_resolve != 0 && (ix->plane > 0 ? ix->plane : ix->ld) <= 1024) {
-            rc = resolve_flagged(ix, nq, k, d_s, d_i, packed, idx_offset, tail_st, false);
+        if (c.margin == 3 && out_dev && ix->opt_resolve != 0 && (c.plane > 0 ? c.plane : c.ld) <= 1024) {
+            rc = resolve_flagged(ix, c, nq, k, d_s, d_i, packed, idx_offset, tail_st, false);
             if (rc) return rc;
             HIP_TRY(hipEventRecord(ix->tail_done[ix->cur_set], tail_st)); // (supersedes the record behind the re-score: the exact
             ix->tail_pending[ix->cur_set] = true;                         // pass reads this set's staged queries)
         }
         return MIPS_OK;
     }
-    rc = finish_margin<KL>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, first_was_optimistic);
-    // the optimistic scan pays while few queries need the second one: after a call that sent more than a quarter there, skip
-    // it for a while
-    if (!rc && first_was_optimistic && ix->opt_f32_fast != 2 && ix->last_flagged >= 64 && ix->last_flagged * 8 > nq) ix->fast_skip = 8;
+    rc = finish_margin<KL>(ix, c, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, pol.recheck);
+    // the optimistic scan pays while few queries need the second one: after a synchronising call that sent more than an eighth
+    // (and at least 64) there, pool_policy skips it for the next 8 calls
+    if (!rc && pol.recheck && ix->opt_f32_fast != 2 && ix->last_flagged >= 64 && ix->last_flagged * 8 > nq) ix->fast_skip = 8;
     return rc;
 }
-
-// "margin_check" as the caller set it -> the mode the code below acts on, for the duration of one call:
-//   1 (default, "auto")  device outputs: 3 = certify on the stream; host buffers: they synchronise anyway and certify
-//   4 ("count only")     1 in the code below: device outputs count flagged queries, nothing more
-// 0 / 2 / 3 as they are.  Restored when the call returns.
-struct MarginScope {
-    mips_index* ix;
-    int keep;
-    MarginScope(mips_index* ix_, bool out_dev) : ix(ix_), keep(ix_->opt_margin) {
-        if (keep == 1 && out_dev) ix->opt_margin = 3;
-        else if (keep == 4) ix->opt_margin = 1;
-    }
-    ~MarginScope() { ix->opt_margin = keep; }
-};
 
 } // namespace

@@ -1,6 +1,7 @@
 // Host side of libmips_hip.so, part 1 of 3 (included by mips_hip.hip, one translation unit): error reporting, device / stream
-// helpers, the index object (storage in HBM, scratch, options, statistics) and what keeps it consistent (growth, phi, row norms,
-// the bf16 image of an fp32-exact index, stream ordering).
+// helpers, the index object (what PERSISTS between calls: storage in HBM, scratch, the caller's options, statistics), the value
+// that describes ONE call in progress (SearchCall: passed by reference, never stored on the index) and what keeps the index
+// consistent (growth, phi, row norms, the bf16 image of an fp32-exact index, stream ordering).
 #pragma once
 
 namespace {
@@ -99,22 +100,11 @@ struct mips_index {
     double* dres2_dev = nullptr; // max_i |x_i - bf16 x_i|^2
     bool dres2_valid = false;
     int opt_f32_fast = 1;        // 0 off, 1 when the call may synchronise (host buffers / margin_check = 2), 2 always
-    bool fast_f32 = false;       // launch_search: stage 1 in progress (index viewed as bf16 rows_hi)
-    // "Optimistic" scan (calls that certify, i.e. may synchronise): pools of 16 / 32 candidates selected from the 16x16x32
-    // kernel's 4 sub-lists of 6 instead of from true K'-entry lists on the 4-wave configuration.  What the pool may have
-    // excluded is bounded all the same (merge_select: sub-lists' last entries), so the margin check decides per query;
-    // flagged queries are re-scanned with true K' = 32 lists.
-    bool optimistic = false;
-    // "margin_check" = 3: device-output searches re-scan the queries they flag WITHOUT a synchronisation -- the flag list is
-    // compacted on the device and the second scan, sized for all queries, lets the workgroups past the count leave
-    const int* nq_dev = nullptr;         // launch_search: device-side query count of the re-scan in progress
     const int* first_nflag_dev = nullptr; // flagged count of the first scan of the last mode-3 search (margin stats)
-    int plane_keep = 0;
     int fast_skip = 0;           // calls left to skip stage 1 for: set by a SYNCHRONISING call that flagged too many queries for the
                                  // optimistic scan to pay (its count is known when it returns; stream-ordered calls never set it,
                                  // so what a search does depends on the calls before it, not on when a device store lands)
     bool phi_valid = false;
-    int call_metric = MIPS_METRIC_IP; // metric of the search in progress (index metric unless MIPS_FORCE_IP)
     bool phi_override = false; // phi was set from outside (global maximum of a sharded index): adds do not reset it
     double phi = 0.0;
     Buffer qbuf, qf32, part_s, part_i, stage, out_s, out_i, scalar, gthr, cand;
@@ -123,7 +113,6 @@ struct mips_index {
     // tuning knobs (mips_index_set_param); 0 = automatic
     int opt_nsplit = 0;
     int opt_qgroups = 0;
-    size_t err_off = 0; // word offset of the scan kernel's error flag inside gthr (0 = none this call)
     int opt_spin_limit = 0; // test-only: polls of the split barrier before a wave gives up (0 = 1 << 22, < 0 = flag forced)
     // sticky scan-error flag: one pinned, mapped host word.  The exact re-score sets it (system-scope store) when
     // the scan kernel of its call gave up on the split barrier; the host reads it without a device round trip.
@@ -132,7 +121,7 @@ struct mips_index {
     char last_kernel[96] = ""; // instance mips_search dispatched last (mips_index_last_kernel)
     // margin check.  0 = off, 1 = flag and count on the device (never synchronises), 2 = certify:
     // synchronise, re-scan the flagged queries with the widest lists.  Host-output searches always certify (they
-    // synchronise anyway) unless the check is off.
+    // synchronise anyway) unless the check is off.  This is the caller's knob: a call acts on margin_mode() of it.
     int opt_margin = 1;
     Buffer mbnd, mflag, qbuf2, qf32b, tmp_s, tmp_i, ids, qhi, qerr2, keyk, qqv, hit_d, hit_i, hit_n, qnorm;
     // wide top-k (mips_search_wide, host_wide.hpp): candidate segments (fixed budget), pools [queries][k'], segment counters,
@@ -160,7 +149,6 @@ struct mips_index {
     int64_t last_flagged = -1, last_rescanned = 0, last_unresolved = 0;
     bool last_fallback = false; // the last search enqueued the gated fall-back re-scan behind its exact pass
     int last_max_n = 0; // flagged queries the exact pass of the last search would resolve at most (statistics: over budget = none settled)
-    int rescan_depth = 0;
     unsigned* last_nflag_dev = nullptr;
     // Split-tail searches (mips_search_split): the scan runs on one stream, select + exact re-score on another, so the
     // NEXT search's scan can start behind this one's.  Two scratch sets alternate; `alt_*` is the one not in use.
@@ -184,7 +172,45 @@ struct mips_index {
     bool has_last = false;
 };
 
+// What ONE launch of a search sees beyond the index: the view of the rows it scans, its staged queries and the switches of the
+// call in progress.  A plain value, built by the entry point (begin_call), passed by reference down to the kernel launch and
+// never stored on the index; a nested launch (stage 1 of the two-stage fp32 search, a re-scan) gets a modified COPY.
+struct SearchCall {
+    const uint8_t* rows = nullptr; // the scanned rows, [capacity][ld]
+    int ld = 0, plane = 0;         // their pitch; plane > 0: the [hi | lo] planes of the fp32-exact index
+    // stage 1 of the two-stage fp32 search: rows = the bf16 rows_hi at pitch hp, scanned like a bf16 index (plane = 0); the
+    // exact re-score and the margin check still run on rows_f32, rescore_ld columns wide
+    bool stage1 = false;
+    int rescore_ld = 0;
+    const void* qbuf = nullptr;    // staged queries: the scan's operand ...
+    const void* qf32 = nullptr;    // ... and the fp32 originals of an fp32-exact index
+    // "Optimistic" scan (calls that certify, i.e. may synchronise): pools of 16 / 32 candidates selected from the sub-lists of
+    // scan_kernel_v4 / k3 instead of from true K'-entry lists.  What the pool may have excluded is bounded all the same
+    // (merge_select: sub-lists' last entries), so the margin check decides per query; flagged queries are re-scanned with true
+    // K' = 32 lists.  Decided by pool_policy, read by choose_scan.
+    bool optimistic = false;
+    bool rescan = false;           // the second scan of flagged queries (widest lists): nothing is prepared for a third
+    // stream-ordered re-scan: the query count lives on the device -- the launches are sized for all queries and the workgroups
+    // past the count leave
+    const int* nq_dev = nullptr;
+    int nsplit = 0;                // index splits asked for (0 = automatic): "nsplit", or a re-scan's own choice
+    bool timed = true;             // the scan may record its event pair and names itself in last_kernel (a nested launch: no)
+    int metric = MIPS_METRIC_IP;   // index metric unless MIPS_FORCE_IP
+    int margin = 0;                // margin_mode() of this call
+};
+
 namespace {
+
+// "margin_check" as the caller set it -> the mode one call acts on:
+//   1 (default, "auto")  device outputs: 3 = certify on the stream; host buffers: they synchronise anyway and certify
+//   4 ("count only")     1: device outputs count flagged queries, nothing more
+// 0 / 2 / 3 as they are.
+inline int margin_mode(const mips_index* ix, bool out_dev) {
+    if (ix->opt_margin == 1 && out_dev) return 3;
+    return ix->opt_margin == 4 ? 1 : ix->opt_margin;
+}
+// The call settles the queries it flags: host buffers (they synchronise anyway), "margin_check" = 2, or on the stream (3)
+inline bool call_certifies(int margin, bool out_dev) { return margin != 0 && (!out_dev || margin >= 2); }
 
 // Rows the per-query buffers (staged queries, insert bounds, partial lists) are padded to: whole query tiles of every kernel that
 // may take the search -- 256 (128 / 256-query tiles), and at bf16 row pitch 1024 also scan_kernel_k3's 192-query tiles

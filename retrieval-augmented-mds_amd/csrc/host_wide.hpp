@@ -90,11 +90,11 @@ int stage_selector(mips_index* ix, Selector& sel, int64_t nq, hipStream_t st) {
 // sel.bits != nullptr: a filtered search (masked scan, certificate on the selected count, masked settlement)
 // sel.qlab != nullptr: a grouped search (grouped scan, certificate without a count, settlement that tests the labels)
 int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool q_dev,
-                Selector sel, hipStream_t st) {
+                Selector sel, int metric, hipStream_t st) {
     const bool grouped = sel.qlab != nullptr;
     const bool masked = sel.bits != nullptr && !grouped;
     const bool f32x = ix->plane > 0;
-    const bool l2 = ix->call_metric == MIPS_METRIC_L2;
+    const bool l2 = metric == MIPS_METRIC_L2;
     const int sld = f32x ? ix->hp : ix->ld;    // row pitch of the scanned bf16 rows
     const int cld = f32x ? ix->plane : ix->ld; // row pitch of the canonical rows and queries
     const int kp = std::min<int>(mips::WIDE_POOL, k + wide_slack(ix, k));

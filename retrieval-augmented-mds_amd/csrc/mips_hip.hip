@@ -1,6 +1,7 @@
 // C ABI of the MI355X MIPS backend (include/mips_hip.h), gfx950 only.  ONE translation unit: the kernels (*.hpp), the host side
 // in three parts -- host_state.hpp (the index object), host_launch.hpp (which kernel answers which search), host_search.hpp (what a
-// search does around its scan) -- and, below, the extern "C" entry points themselves.
+// search does around its scan) -- and, below, the extern "C" entry points themselves.  The search entry points validate their
+// arguments and then share one prologue (run_call), which hands their body the SearchCall of the whole index.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -358,149 +359,122 @@ int mips_synth_fill(void* out_device, int64_t n, int64_t d, int64_t row0, uint64
     return MIPS_OK;
 }
 
-static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
-                       int64_t idx_offset, int flags, void* hip_stream, void* tail_stream);
+} // extern "C"
 
-int mips_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
-                int64_t idx_offset, int flags, void* hip_stream) {
-    return search_impl(ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, hip_stream, hip_stream);
+namespace {
+
+// The call value of a search over the whole index as it stands (scan_and_finish and rescan_flagged derive their nested
+// launches' views from it); the staged query buffers are filled in once they are staged
+SearchCall index_call(const mips_index* ix, int flags) {
+    SearchCall c;
+    c.rows = ix->rows;
+    c.ld = ix->ld;
+    c.plane = ix->plane;
+    c.nsplit = ix->opt_nsplit;
+    c.metric = (flags & MIPS_FORCE_IP) ? MIPS_METRIC_IP : ix->metric;
+    c.margin = margin_mode(ix, (flags & MIPS_OUT_DEVICE) != 0);
+    return c;
 }
 
-int mips_search_split(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
-                      int64_t idx_offset, int flags, void* scan_stream, void* tail_stream) {
-    if (!(flags & MIPS_OUT_DEVICE)) return fail(MIPS_E_INVALID, "mips_search_split: device outputs only (MIPS_OUT_DEVICE)");
-    return search_impl(ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, scan_stream, tail_stream);
-}
-
-static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
-                       int64_t idx_offset, int flags, void* hip_stream, void* tail_stream) {
-    if (!ix) return fail(MIPS_E_INVALID, "mips_search: index is NULL");
-    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_search: negative nq or k");
-    if (k > MIPS_MAX_K) return fail(MIPS_E_UNSUPPORTED, "mips_search: k = %d exceeds MIPS_MAX_K = %d", k, MIPS_MAX_K);
-    if (!src_dtype_ok(ix, q_dtype, true)) return fail(MIPS_E_INVALID, "mips_search: q_dtype must be F32 or BF16 (or FP8_E4M3 bytes for an all-e4m3 index)");
-    if (nq == 0 || k == 0) return MIPS_OK;
-    if (!q || !out_idx || (!out_scores && !(flags & MIPS_OUT_PACKED))) return fail(MIPS_E_INVALID, "mips_search: NULL buffer");
-    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_search: more than 2^24 queries in one call");
+// What mips_search, the wide and the range search do between validating their arguments and their own work, in this order:
+// make the index's device current; report an earlier device-output search on this index whose scan timed out (no
+// synchronisation: the word lives in host memory) before anything new is enqueued; order the call behind the last one on
+// another stream; split-tail form: take the other scratch set, so that this scan may run while the previous search's tail still
+// reads its lists; whichever set is about to be used, a tail still pending on it (it reads the set's staged queries) comes
+// first.  body(c) is the rest of the call.
+template <class Body>
+int run_call(const char* who, mips_index* ix, int flags, hipStream_t st, bool split, Body body) {
     DeviceGuard g(ix->device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    {   // an earlier device-output search on this index whose scan timed out: report it now (no synchronisation:
-        // the word lives in host memory), before anything new is enqueued
-        const int prev = take_scan_error(ix, "mips_search");
-        if (prev) return prev;
-    }
+    const int prev = take_scan_error(ix, who);
+    if (prev) return prev;
     ORDER_ON(ix, st);
-    const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
-    const bool packed = (flags & MIPS_OUT_PACKED) != 0;
-    ix->call_metric = (flags & MIPS_FORCE_IP) ? MIPS_METRIC_IP : ix->metric;
-    if (packed && !out_dev) return fail(MIPS_E_INVALID, "mips_search: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE");
-    // split-tail form: the other scratch set, so that this scan may run while the previous search's tail still reads
-    // its lists; whichever set is about to be used, a tail still pending on it comes first
-    hipStream_t tail_st = (hipStream_t)tail_stream;
-    const bool split = tail_st != st;
     if (split) swap_scratch_sets(ix);
     if (ix->tail_pending[ix->cur_set]) {
         HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[ix->cur_set], 0));
         ix->tail_pending[ix->cur_set] = false;
     }
+    SearchCall c = index_call(ix, flags);
+    return body(c);
+}
 
+// Host-output calls compute into the index's own device buffers (n scores and indices), copied out when the call ends
+int device_outputs(mips_index* ix, bool out_dev, int64_t n, float*& d_s, int64_t*& d_i) {
+    if (out_dev) return MIPS_OK;
+    int rc = ix->out_s.ensure((size_t)n * sizeof(float));
+    if (rc) return rc;
+    rc = ix->out_i.ensure((size_t)n * sizeof(int64_t));
+    if (rc) return rc;
+    d_s = (float*)ix->out_s.p;
+    d_i = (int64_t*)ix->out_i.p;
+    return MIPS_OK;
+}
+
+// mips_search / mips_search_split behind run_call: the one-launch kernel or stage queries -> pool_policy -> scan_and_finish<K'>
+int search_call(mips_index* ix, SearchCall& c, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx, int64_t idx_offset,
+                int flags, hipStream_t st, hipStream_t tail_st) {
+    const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
+    const bool packed = (flags & MIPS_OUT_PACKED) != 0;
+    const bool q_dev = (flags & MIPS_Q_DEVICE) != 0;
+    const bool split = tail_st != st;
+    if (packed && !out_dev) return fail(MIPS_E_INVALID, "mips_search: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE");
     float* d_s = out_scores;
     int64_t* d_i = out_idx;
-    if (!out_dev) {
-        int rc = ix->out_s.ensure((size_t)nq * k * sizeof(float));
+    int rc = device_outputs(ix, out_dev, nq * k, d_s, d_i);
+    if (rc) return rc;
+    if (ix->ntotal > 0 && c.metric == MIPS_METRIC_L2) {
+        rc = compute_phi(ix, st);
         if (rc) return rc;
-        rc = ix->out_i.ensure((size_t)nq * k * sizeof(int64_t));
-        if (rc) return rc;
-        d_s = (float*)ix->out_s.p;
-        d_i = (int64_t*)ix->out_i.p;
     }
-
-    MarginScope margin_scope(ix, out_dev);
-    const bool certifies = ix->opt_margin != 0 && (!out_dev || ix->opt_margin >= 2);
-    bool done = false;
+    const bool certifies = call_certifies(c.margin, out_dev);
     if (ix->ntotal == 0) {
         const int64_t total = nq * k;
-        mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, packed ? d_i : nullptr, total, ix->call_metric);
+        mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, packed ? d_i : nullptr, total, c.metric);
         HIP_TRY(hipGetLastError());
-        done = true;
     } else if (tiny_eligible(ix, nq, k, certifies)) {
         // the reference's own call shape (<= 16 queries, small knowledge base): one launch (tiny_search.hpp)
-        if (ix->call_metric == MIPS_METRIC_L2) {
-            int rc = compute_phi(ix, st);
-            if (rc) return rc;
-        }
         const void* qd = q;
-        if (!(flags & MIPS_Q_DEVICE)) {
+        if (!q_dev) {
             const size_t qbytes = (size_t)nq * ix->d * (q_dtype == MIPS_DTYPE_F32 ? 4 : 2);
-            int rc = ix->stage.ensure(qbytes);
+            rc = ix->stage.ensure(qbytes);
             if (rc) return rc;
             HIP_TRY(hipMemcpyAsync(ix->stage.p, q, qbytes, hipMemcpyHostToDevice, st));
             qd = ix->stage.p;
         }
-        int rc = tiny_search(ix, qd, q_dtype, nq, k, k, 0, nullptr, d_s, d_i, packed, idx_offset, st, certifies);
+        rc = tiny_search(ix, c, qd, q_dtype, nq, k, k, 0, nullptr, d_s, d_i, packed, idx_offset, st, certifies);
         if (rc) return rc;
-        done = true;
         if (certifies) {
             // the exact pass behind the one launch (the kernel, and with it its results, live on the scan stream even in the
             // split-tail form).  Device outputs: enqueued blind, it leaves at once when nothing was flagged; host buffers and
             // "margin_check" = 2 synchronise, read the count and skip it when that is 0
-            rc = resolve_flagged(ix, nq, k, d_s, d_i, packed, idx_offset, st, /*certify_now=*/!(out_dev && ix->opt_margin == 3), /*skip_compact=*/true);
+            rc = resolve_flagged(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, /*certify_now=*/!(out_dev && c.margin == 3), /*skip_compact=*/true);
             if (rc < 0) return rc; // (kUseRescan cannot happen: <= 16 queries)
         }
-    }
-    if (!done) {
-        if (ix->call_metric == MIPS_METRIC_L2) {
-            int rc = compute_phi(ix, st);
-            if (rc) return rc;
-        }
+    } else {
+        // stage the queries: converted to the scan's operand type, zero-padded to whole query tiles; the fp32 originals of an
+        // fp32-exact index next to them; the scan's shared insert bounds (8 class words per query + the error word) cleared
         const int64_t nq_pad = query_pad(ix, nq);
         const size_t row_bytes = (size_t)ix->ld * ix->qsize;
-        int rc = ix->qbuf.ensure((size_t)nq_pad * row_bytes);
+        rc = ix->qbuf.ensure((size_t)nq_pad * row_bytes);
         if (rc) return rc;
         uint8_t* qb = (uint8_t*)ix->qbuf.p;
-        float* qkeep = nullptr;
-        if (ix->plane > 0) {
-            rc = ix->qf32.ensure((size_t)nq_pad * ix->plane * sizeof(float));
-            if (rc) return rc;
-            qkeep = (float*)ix->qf32.p;
-        }
-        // shared insert bounds of the scan: 8 class words per query + the error word
         const int64_t thr_words = nq_pad * 8 + 4;
         rc = ix->gthr.ensure((size_t)thr_words * sizeof(unsigned));
         if (rc) return rc;
         if (ix->plane > 0) { // fp32-exact staging has its own kernel: clear with plain memsets
-            rc = convert_into(ix, q, nq, q_dtype, (flags & MIPS_Q_DEVICE) ? 1 : 0, qb, st, qkeep);
+            rc = ix->qf32.ensure((size_t)nq_pad * ix->plane * sizeof(float));
+            if (rc) return rc;
+            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, (float*)ix->qf32.p);
             if (rc) return rc;
             if (nq_pad > nq) HIP_TRY(hipMemsetAsync(qb + (size_t)nq * row_bytes, 0, (size_t)(nq_pad - nq) * row_bytes, st));
             HIP_TRY(hipMemsetAsync(ix->gthr.p, 0, (size_t)thr_words * sizeof(unsigned), st));
         } else { // one launch converts the queries, zero-pads to the tile multiple and clears the bounds
-            rc = convert_into(ix, q, nq, q_dtype, (flags & MIPS_Q_DEVICE) ? 1 : 0, qb, st, qkeep, nq_pad - nq,
-                              (uint32_t*)ix->gthr.p, thr_words, ix->qsize);
+            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, nullptr, nq_pad - nq, (uint32_t*)ix->gthr.p, thr_words, ix->qsize);
             if (rc) return rc;
         }
-        // The MFMA scores only SELECT a pool of K' candidates that is then re-scored exactly.
-        // Pool K' = 8 / 10 / 16 / 32 >= k + 3.  What is GUARANTEED to reach the pool per (query, split): the 32x32
-        // kernels (scan_kernel_v3 / f8 / generic) keep lists of K' entries, so MFMA ranks 1 .. K'; the 16x16 kernels
-        // (scan_kernel_v4 / f8x: bf16 pitch 384 .. 768 or fp8 pitch <= 768, k <= 5, more than one query tile) keep 4
-        // sub-lists of 6, so MFMA ranks 1 .. 6 = k + 1 for certain and 7 .. 8 unless 6 better documents share the
-        // sub-list (rows congruent mod 16 within a split).  Queries whose k-th exact score is too close to what the
-        // pool may have lost are detected by the re-score and re-scanned with the widest lists (margin check below).
-        // fp32-exact index: two-stage search when the call may synchronise anyway (see mips_index: rows_hi).  Stage 1 keeps
-        // K' = 32 lists where the bf16 kernels have them (pitch 256 / 512 / 768): the pool's bound is then the ~33rd best
-        // score, far enough below the k-th for the widened margin to certify nearly every query on well-separated data
-        // (with K' = 8 pools 44 % of the queries of a Gaussian test set went to the second stage; pitch 1024 has no more).
-        const bool hi_long = ix->hp > 0 && ix->hp <= 1024;
-        // (round 3: row pitch 1024 has true K' = 32 lists as well -- with pools of 8, all it had before, 46 % of a Gaussian
-        // test set went to the second stage and stage 1 did not pay)
-        // k <= 13 only: the pool is 32 wide whatever k, and the widened margin (representation error of bf16(x) . bf16(q)) has to
-        // fit between the k-th and the 33rd score -- at k = 20 .. 29 nearly every query of a Gaussian test set was flagged, and an
-        // exact pass per 8 flagged queries costs far more than the three-segment scan saves
-        bool fast = ix->plane > 0 && ix->hp > 0 && hi_long && k <= 13 && ix->opt_f32_fast != 0 && ix->opt_margin != 0 && !split &&
-                    (ix->opt_f32_fast == 2 || !out_dev || ix->opt_margin >= 2);
-        if (fast && ix->opt_f32_fast == 1 && ix->fast_skip > 0) {
-            --ix->fast_skip;
-            fast = false;
-        }
-        if (fast) { // bf16(q) at the bf16 kernels' row pitch, |q - bf16 q|^2, bf16 rows and residual bound up to date
+        c.qbuf = ix->qbuf.p;
+        c.qf32 = ix->qf32.p;
+        const PoolPolicy pol = pool_policy(ix, nq, k, out_dev, split, c.margin);
+        if (pol.fast) { // bf16(q) at the bf16 kernels' row pitch, |q - bf16 q|^2, bf16 rows and residual bound up to date
             rc = ix->qhi.ensure((size_t)nq_pad * ix->hp * 2);
             if (rc) return rc;
             rc = ix->qerr2.ensure((size_t)nq * sizeof(double));
@@ -511,43 +485,14 @@ static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq,
             HIP_TRY(hipGetLastError());
             rc = ensure_hi(ix, st);
             if (rc) return rc;
-            rc = ensure_xmax2(ix, st); // (on the fp32 rows: before the index is viewed as rows_hi)
+            rc = ensure_xmax2(ix, st); // (on the fp32 rows)
             if (rc) return rc;
         }
-        // (pools of 32, not 16: with the 16th best score as the bound 30 of 4096 Gaussian queries went to the second stage, and
-        // a second stage of even one query tile costs more than stage 1 saved -- 22 ms per call instead of 5.4)
-        // bf16 rows at pitch 1024, k <= 5, a large index, a call that certifies: pool of 16 (scan_kernel_k3 with every sub-list
-        // vouching for its 2nd best).  The MFMA error bound at K = 1024 (0.14 on unit-variance data) reaches from the 5th exact score
-        // to the 8th best approximate one for one Gaussian query in ~3000 at 2^22 rows, and each flagged query costs a pass over the
-        // index (3 ms there); the 16th best is out of reach.  Small indexes keep the pool of 8 (their exact pass is cheap).
-        bool deep_1024 = !fast && k <= 5 && ix->plane == 0 && ix->esize == 2 && !ix->mixed && ix->ld == 1024 && nq > 256 && ix->ntotal >= (1ll << 21) &&
-                         ix->opt_margin != 0 && !split && (!out_dev || ix->opt_margin >= 2) && ix->opt_f32_fast != 0 &&
-                         ix->opt_variant == 0; // (forced kernels keep the pool of 8)
-        if (deep_1024 && ix->fast_skip > 0) {
-            --ix->fast_skip;
-            deep_1024 = false;
-        }
-        if (fast && hi_long) {
-            rc = scan_and_finish<32>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split, true);
-        } else if (k <= 5 && deep_1024) {
-            rc = scan_and_finish<16>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split, false, true);
-        } else if (k <= 5) {
-            rc = scan_and_finish<8>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split, fast);
-        } else if (k <= 7) { // k + 1 = 6 is what Mips.search fetches for top_k = 5 with ignore_indexes (mips.py:388-398)
-            rc = scan_and_finish<10>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split, fast);
-        } else {
-            // bf16 index, a call that certifies, 8 <= k <= 29: pool of 32 out of the 16x16x32 kernel's sub-lists (see
-            // mips_index::optimistic; round 3: k = 14 .. 29 as well -- the class words vouch for 32 documents, what the
-            // sub-lists of 6 may have dropped is bounded, the margin check decides per query).  Otherwise true K' = 16 / 32 lists.
-            bool opt = ix->plane == 0 && ix->esize == 2 && !ix->mixed && ix->opt_margin != 0 && !split && (!out_dev || ix->opt_margin >= 2) &&
-                       ix->opt_f32_fast != 0 && ((ix->ld % 128 == 0 && ix->ld >= 384 && ix->ld <= 768) || (ix->ld == 1024 && nq > 256));
-            if (opt && ix->fast_skip > 0) {
-                --ix->fast_skip;
-                opt = false;
-            }
-            if (opt) rc = scan_and_finish<32>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split, false, true);
-            else if (k <= 13) rc = scan_and_finish<16>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split, false);
-            else rc = scan_and_finish<32>(ix, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split, false);
+        switch (pol.kl) {
+        case 8: rc = scan_and_finish<8>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
+        case 10: rc = scan_and_finish<10>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
+        case 16: rc = scan_and_finish<16>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
+        default: rc = scan_and_finish<32>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
         }
         if (rc) return rc;
     }
@@ -562,17 +507,33 @@ static int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq,
     return MIPS_OK;
 }
 
-// sel_bits == NULL: the unfiltered search (sel_nbits and sel_bit0 are not looked at); q_labels == NULL: no group filter
-static int search_wide_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
-                            int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream,
-                            const int32_t* q_labels = nullptr, int grp_mode = 0) {
-    if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
-    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "%s: negative nq or k", who);
-    if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "%s: k = %d exceeds MIPS_MAX_K_WIDE = %d", who, k, MIPS_MAX_K_WIDE);
+int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx, int64_t idx_offset, int flags,
+                void* hip_stream, void* tail_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "mips_search: index is NULL");
+    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_search: negative nq or k");
+    if (k > MIPS_MAX_K) return fail(MIPS_E_UNSUPPORTED, "mips_search: k = %d exceeds MIPS_MAX_K = %d", k, MIPS_MAX_K);
+    if (!src_dtype_ok(ix, q_dtype, true)) return fail(MIPS_E_INVALID, "mips_search: q_dtype must be F32 or BF16 (or FP8_E4M3 bytes for an all-e4m3 index)");
+    if (nq == 0 || k == 0) return MIPS_OK;
+    if (!q || !out_idx || (!out_scores && !(flags & MIPS_OUT_PACKED))) return fail(MIPS_E_INVALID, "mips_search: NULL buffer");
+    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_search: more than 2^24 queries in one call");
+    const hipStream_t st = (hipStream_t)hip_stream, tail_st = (hipStream_t)tail_stream;
+    return run_call("mips_search", ix, flags, st, tail_st != st, [&](SearchCall& c) {
+        return search_call(ix, c, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, st, tail_st);
+    });
+}
+
+// ---- The wide and the range search (and their filtered / grouped forms) validate the same way and build the same Selector
+// what both serve: bf16 and fp32-exact indexes of up to 1024 columns, float32 or bf16 queries
+int check_served(const char* who, const mips_index* ix, int q_dtype) {
     if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "%s: e4m3 storage is not served (bf16 and fp32-exact indexes only)", who);
     if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
         return fail(MIPS_E_UNSUPPORTED, "%s: stored rows of more than 1024 columns are not served", who);
     if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "%s: q_dtype must be F32 or BF16", who);
+    return MIPS_OK;
+}
+// sel_bits == NULL: the unfiltered search (sel_nbits and sel_bit0 are not looked at); q_labels == NULL: no group filter
+int make_selector(const char* who, const mips_index* ix, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0,
+                  const int32_t* q_labels, int grp_mode, Selector& sel) {
     if (sel_bits && (sel_bit0 < 0 || sel_nbits < 0 || sel_bit0 > sel_nbits || ix->ntotal > sel_nbits - sel_bit0))
         return fail(MIPS_E_INVALID, "%s: the selector's %lld bits from bit %lld on do not cover the index's %lld rows", who, (long long)sel_nbits,
                     (long long)sel_bit0, (long long)ix->ntotal);
@@ -582,66 +543,132 @@ static int search_wide_impl(const char* who, mips_index_t* ix, const void* q, in
             return fail(MIPS_E_INVALID, "%s: %lld of the index's %lld rows carry a label (mips_index_set_labels)", who, (long long)ix->nlabelled,
                         (long long)ix->ntotal);
     }
+    sel.bits = sel_bits;
+    sel.nbits = sel_nbits;
+    sel.bit0 = sel_bit0;
+    sel.dev = (flags & MIPS_SEL_DEVICE) != 0;
+    sel.qlab = q_labels;
+    sel.qlab_dev = (flags & MIPS_GRP_DEVICE) != 0;
+    sel.grp_only = grp_mode == MIPS_GRP_ONLY ? 1 : 0;
+    return MIPS_OK;
+}
+
+int search_wide_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                     int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream,
+                     const int32_t* q_labels = nullptr, int grp_mode = 0) {
+    if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
+    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "%s: negative nq or k", who);
+    if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "%s: k = %d exceeds MIPS_MAX_K_WIDE = %d", who, k, MIPS_MAX_K_WIDE);
+    int rc = check_served(who, ix, q_dtype);
+    if (rc) return rc;
+    Selector sel;
+    rc = make_selector(who, ix, flags, sel_bits, sel_nbits, sel_bit0, q_labels, grp_mode, sel);
+    if (rc) return rc;
     if (nq == 0 || k == 0) return MIPS_OK;
+    const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
     const bool packed = (flags & MIPS_OUT_PACKED) != 0;
-    if (packed && !(flags & MIPS_OUT_DEVICE)) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE", who);
+    if (packed && !out_dev) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED requires MIPS_OUT_DEVICE", who);
     if (!q || !out_idx || (!out_scores && !packed)) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
     if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "%s: more than 2^24 queries in one call", who);
-    DeviceGuard g(ix->device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    {
-        const int prev = take_scan_error(ix, who);
-        if (prev) return prev;
-    }
-    ORDER_ON(ix, st);
-    if (ix->tail_pending[ix->cur_set]) { // a split-tail search still reading the staged queries of this scratch set
-        HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[ix->cur_set], 0));
-        ix->tail_pending[ix->cur_set] = false;
-    }
+    const hipStream_t st = (hipStream_t)hip_stream;
+    return run_call(who, ix, flags, st, false, [&](SearchCall& c) {
+        float* d_s = out_scores;
+        int64_t* d_i = out_idx;
+        int rc = device_outputs(ix, out_dev, nq * k, d_s, d_i);
+        if (rc) return rc;
+        if (ix->ntotal == 0) {
+            const int64_t total = nq * k;
+            mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, packed ? d_i : nullptr, total, c.metric);
+            HIP_TRY(hipGetLastError());
+            ix->last_flagged = 0;
+            ix->last_rescanned = 0;
+            ix->last_unresolved = 0;
+            ix->first_nflag_dev = nullptr;
+        } else {
+            rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, c.metric, st);
+            if (rc) return rc;
+        }
+        if (!out_dev) {
+            if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host, 64, hipHostMallocDefault));
+            HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            if (ix->ntotal > 0) HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->first_nflag_dev, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (ix->ntotal > 0) {
+                ix->last_flagged = (int64_t)ix->nflag_host[0];
+                ix->last_rescanned = ix->last_flagged;
+            }
+        }
+        return (int)MIPS_OK;
+    });
+}
+
+int range_search_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
+                      float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, const uint8_t* sel_bits,
+                      int64_t sel_nbits, int64_t sel_bit0, void* hip_stream, const int32_t* q_labels = nullptr, int grp_mode = 0) {
+    if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
+    if (nq < 0 || cap < 0) return fail(MIPS_E_INVALID, "%s: negative nq or cap", who);
+    if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED does not apply to a CSR result", who);
+    int rc = check_served(who, ix, q_dtype);
+    if (rc) return rc;
+    if (!out_lims || (nq > 0 && (!q || !radii)) || (cap > 0 && (!out_scores || !out_idx))) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
+    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "%s: more than 2^24 queries in one call", who);
+    Selector sel;
+    rc = make_selector(who, ix, flags, sel_bits, sel_nbits, sel_bit0, q_labels, grp_mode, sel);
+    if (rc) return rc;
+    for (int64_t j = 0; j < nq; ++j)
+        if (radii[j] != radii[j]) return fail(MIPS_E_INVALID, "%s: radii[%lld] is NaN", who, (long long)j);
     const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
-    ix->call_metric = (flags & MIPS_FORCE_IP) ? MIPS_METRIC_IP : ix->metric;
-    float* d_s = out_scores;
-    int64_t* d_i = out_idx;
-    if (!out_dev) {
-        int rc = ix->out_s.ensure((size_t)nq * k * sizeof(float));
+    const hipStream_t st = (hipStream_t)hip_stream;
+    return run_call(who, ix, flags, st, false, [&](SearchCall& c) {
+        int64_t* d_lims = out_lims;
+        float* d_s = out_scores;
+        int64_t* d_i = out_idx;
+        int rc = device_outputs(ix, out_dev, cap, d_s, d_i);
         if (rc) return rc;
-        rc = ix->out_i.ensure((size_t)nq * k * sizeof(int64_t));
-        if (rc) return rc;
-        d_s = (float*)ix->out_s.p;
-        d_i = (int64_t*)ix->out_i.p;
-    }
-    if (ix->ntotal == 0) {
-        const int64_t total = nq * k;
-        mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, packed ? d_i : nullptr, total, ix->call_metric);
-        HIP_TRY(hipGetLastError());
+        if (!out_dev) {
+            rc = ix->r_lims.ensure((size_t)(nq + 1) * sizeof(int64_t));
+            if (rc) return rc;
+            d_lims = (int64_t*)ix->r_lims.p;
+        }
+        if (nq == 0 || ix->ntotal == 0) { // no hits: every limit is 0
+            HIP_TRY(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st));
+        } else {
+            rc = range_search(ix, q, q_dtype, nq, radii, d_lims, d_s, d_i, cap, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, c.metric, st);
+            if (rc) return rc;
+        }
+        // nothing is ever uncertified: the candidates are a provable superset and the filter decides on the canonical score
         ix->last_flagged = 0;
         ix->last_rescanned = 0;
         ix->last_unresolved = 0;
+        ix->last_max_n = 0;
+        ix->last_fallback = false;
         ix->first_nflag_dev = nullptr;
-    } else {
-        Selector sel;
-        sel.bits = sel_bits;
-        sel.nbits = sel_nbits;
-        sel.bit0 = sel_bit0;
-        sel.dev = (flags & MIPS_SEL_DEVICE) != 0;
-        sel.qlab = q_labels;
-        sel.qlab_dev = (flags & MIPS_GRP_DEVICE) != 0;
-        sel.grp_only = grp_mode == MIPS_GRP_ONLY ? 1 : 0;
-        const int rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, st);
-        if (rc) return rc;
-    }
-    if (!out_dev) {
-        if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host, 64, hipHostMallocDefault));
-        HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (ix->ntotal > 0) HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->first_nflag_dev, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (ix->ntotal > 0) {
-            ix->last_flagged = (int64_t)ix->nflag_host[0];
-            ix->last_rescanned = ix->last_flagged;
+        if (!out_dev) {
+            HIP_TRY(hipMemcpyAsync(out_lims, d_lims, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            if (cap > 0) {
+                HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)cap * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            }
+            HIP_TRY(hipStreamSynchronize(st));
         }
-    }
-    return MIPS_OK;
+        return (int)MIPS_OK;
+    });
+}
+
+} // namespace
+
+extern "C" {
+
+int mips_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                int64_t idx_offset, int flags, void* hip_stream) {
+    return search_impl(ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, hip_stream, hip_stream);
+}
+
+int mips_search_split(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                      int64_t idx_offset, int flags, void* scan_stream, void* tail_stream) {
+    if (!(flags & MIPS_OUT_DEVICE)) return fail(MIPS_E_INVALID, "mips_search_split: device outputs only (MIPS_OUT_DEVICE)");
+    return search_impl(ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, scan_stream, tail_stream);
 }
 
 int mips_search_wide(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx,
@@ -653,88 +680,6 @@ int mips_search_wide_sel(mips_index_t* ix, const void* q, int q_dtype, int64_t n
                          int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
     return search_wide_impl("mips_search_wide_sel", ix, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, sel_bits, sel_nbits, sel_bit0,
                             hip_stream);
-}
-
-static int range_search_impl(const char* who, mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims,
-                             float* out_scores, int64_t* out_idx, int64_t cap, int64_t idx_offset, int flags, const uint8_t* sel_bits,
-                             int64_t sel_nbits, int64_t sel_bit0, void* hip_stream, const int32_t* q_labels = nullptr, int grp_mode = 0) {
-    if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
-    if (nq < 0 || cap < 0) return fail(MIPS_E_INVALID, "%s: negative nq or cap", who);
-    if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED does not apply to a CSR result", who);
-    if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "%s: e4m3 storage is not served (bf16 and fp32-exact indexes only)", who);
-    if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
-        return fail(MIPS_E_UNSUPPORTED, "%s: stored rows of more than 1024 columns are not served", who);
-    if (q_dtype != MIPS_DTYPE_F32 && q_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "%s: q_dtype must be F32 or BF16", who);
-    if (!out_lims || (nq > 0 && (!q || !radii)) || (cap > 0 && (!out_scores || !out_idx))) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
-    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "%s: more than 2^24 queries in one call", who);
-    if (sel_bits && (sel_bit0 < 0 || sel_nbits < 0 || sel_bit0 > sel_nbits || ix->ntotal > sel_nbits - sel_bit0))
-        return fail(MIPS_E_INVALID, "%s: the selector's %lld bits from bit %lld on do not cover the index's %lld rows", who, (long long)sel_nbits,
-                    (long long)sel_bit0, (long long)ix->ntotal);
-    if (q_labels) {
-        if (grp_mode != MIPS_GRP_EXCLUDE && grp_mode != MIPS_GRP_ONLY) return fail(MIPS_E_INVALID, "%s: grp_mode must be 0 (exclude) or 1 (only), got %d", who, grp_mode);
-        if (ix->nlabelled != ix->ntotal)
-            return fail(MIPS_E_INVALID, "%s: %lld of the index's %lld rows carry a label (mips_index_set_labels)", who, (long long)ix->nlabelled,
-                        (long long)ix->ntotal);
-    }
-    for (int64_t j = 0; j < nq; ++j)
-        if (radii[j] != radii[j]) return fail(MIPS_E_INVALID, "%s: radii[%lld] is NaN", who, (long long)j);
-    DeviceGuard g(ix->device);
-    hipStream_t st = (hipStream_t)hip_stream;
-    {
-        const int prev = take_scan_error(ix, who);
-        if (prev) return prev;
-    }
-    ORDER_ON(ix, st);
-    if (ix->tail_pending[ix->cur_set]) { // a split-tail search still reading the staged queries of this scratch set
-        HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[ix->cur_set], 0));
-        ix->tail_pending[ix->cur_set] = false;
-    }
-    const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
-    ix->call_metric = (flags & MIPS_FORCE_IP) ? MIPS_METRIC_IP : ix->metric;
-    int64_t* d_lims = out_lims;
-    float* d_s = out_scores;
-    int64_t* d_i = out_idx;
-    if (!out_dev) {
-        int rc = ix->r_lims.ensure((size_t)(nq + 1) * sizeof(int64_t));
-        if (rc) return rc;
-        rc = ix->out_s.ensure((size_t)cap * sizeof(float));
-        if (rc) return rc;
-        rc = ix->out_i.ensure((size_t)cap * sizeof(int64_t));
-        if (rc) return rc;
-        d_lims = (int64_t*)ix->r_lims.p;
-        d_s = (float*)ix->out_s.p;
-        d_i = (int64_t*)ix->out_i.p;
-    }
-    if (nq == 0 || ix->ntotal == 0) { // no hits: every limit is 0
-        HIP_TRY(hipMemsetAsync(d_lims, 0, (size_t)(nq + 1) * sizeof(int64_t), st));
-    } else {
-        Selector sel;
-        sel.bits = sel_bits;
-        sel.nbits = sel_nbits;
-        sel.bit0 = sel_bit0;
-        sel.dev = (flags & MIPS_SEL_DEVICE) != 0;
-        sel.qlab = q_labels;
-        sel.qlab_dev = (flags & MIPS_GRP_DEVICE) != 0;
-        sel.grp_only = grp_mode == MIPS_GRP_ONLY ? 1 : 0;
-        const int rc = range_search(ix, q, q_dtype, nq, radii, d_lims, d_s, d_i, cap, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, st);
-        if (rc) return rc;
-    }
-    // nothing is ever uncertified: the candidates are a provable superset and the filter decides on the canonical score
-    ix->last_flagged = 0;
-    ix->last_rescanned = 0;
-    ix->last_unresolved = 0;
-    ix->last_max_n = 0;
-    ix->last_fallback = false;
-    ix->first_nflag_dev = nullptr;
-    if (!out_dev) {
-        HIP_TRY(hipMemcpyAsync(out_lims, d_lims, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        if (cap > 0) {
-            HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)cap * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)cap * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return MIPS_OK;
 }
 
 int mips_range_search(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const float* radii, int64_t* out_lims, float* out_scores,
@@ -783,22 +728,21 @@ int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64
     }
     ORDER_ON(ix, st);
     {
-        MarginScope margin_scope(ix, /*out_dev=*/true);
-        const bool certifies = ix->opt_margin >= 2;
+        SearchCall c = index_call(ix, MIPS_OUT_DEVICE);
+        const bool certifies = call_certifies(c.margin, /*out_dev=*/true);
         if (tiny_eligible(ix, nq, k_fetch, certifies)) {
-            ix->call_metric = ix->metric;
-            if (ix->call_metric == MIPS_METRIC_L2) {
+            if (c.metric == MIPS_METRIC_L2) {
                 int rc = compute_phi(ix, st);
                 if (rc) return rc;
             }
-            int rc = tiny_search(ix, q_device, q_dtype, nq, k_fetch, k, normalize, ignore_device, out_scores_device, out_idx_device, false,
+            int rc = tiny_search(ix, c, q_device, q_dtype, nq, k_fetch, k, normalize, ignore_device, out_scores_device, out_idx_device, false,
                                  idx_offset, st, certifies);
             if (rc) return rc;
             if (!certifies) return MIPS_OK; // ("margin_check" = 4 / 0: flagged queries are counted, or not even that)
             // certified: the exact pass behind the one launch ranks the hits of a flagged query and applies the same ignore
             // filter -- without a synchronisation by default (it leaves at once when nothing was flagged); "margin_check" = 2
             // synchronises to read the counts
-            rc = resolve_flagged(ix, nq, k_fetch, out_scores_device, out_idx_device, false, idx_offset, st, /*certify_now=*/ix->opt_margin == 2,
+            rc = resolve_flagged(ix, c, nq, k_fetch, out_scores_device, out_idx_device, false, idx_offset, st, /*certify_now=*/c.margin == 2,
                                  /*skip_compact=*/true, ignore_device, k);
             return rc < 0 ? rc : MIPS_OK;
         }
