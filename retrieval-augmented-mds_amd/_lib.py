@@ -19,6 +19,7 @@ LIB_DIR = os.path.join(_HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmips_hip.so")
 HEADER = os.path.join(_ROOT, "include", "mips_hip.h")
 HEADER_SHARDED = os.path.join(_ROOT, "include", "mips_hip_sharded.h")  # helpers of the shard exchange (no index handle)
+HEADER_UPDATE = os.path.join(_ROOT, "include", "mips_hip_update.h")  # calls that change the rows an index holds
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -38,7 +39,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -138,7 +139,10 @@ def _bind(lib):
     sig_sharded = {  # include/mips_hip_sharded.h
         "mips_range_merge_records": (i32, [vp, i32, i64, i64, vp, vp, vp, i64, vp, i32, vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded}.items():
+    sig_update = {  # include/mips_hip_update.h
+        "mips_index_remove": (i32, [vp, vp, i64, i64, i32, c.POINTER(i64), vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -158,6 +162,7 @@ EXPORTS = (
 )
 
 EXPORTS_SHARDED = ("mips_range_merge_records",)  # what include/mips_hip_sharded.h declares; the same library exports it
+EXPORTS_UPDATE = ("mips_index_remove",)  # what include/mips_hip_update.h declares; the same library exports it
 
 
 def range_record_words(nq: int, stride: int) -> int:

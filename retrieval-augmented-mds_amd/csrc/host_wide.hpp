@@ -46,26 +46,37 @@ struct Selector {
 // shifted, cleared and padded words of select_kernels.hpp, and their popcount.  Nothing is read back.
 // A grouped call without a bitmap stages all ones over [0, ntotal), and every grouped call stages its query labels: a slice reads
 // them at its offset (a multiple of the query tile), the last one up to the pad.
+// The caller's bitmap as the staging kernels take it (device bytes, their number, the bit of local row 0): a host bitmap is
+// copied with the stream's async copy (the removal's staging, host_remove.hpp, starts the same way)
+int bitmap_on_device(mips_index* ix, const uint8_t* bits, int64_t nbits, int64_t sel_bit0, bool dev, hipStream_t st, const uint8_t*& src,
+                     int64_t& bit0, int64_t& nbytes) {
+    src = bits;
+    bit0 = sel_bit0;
+    nbytes = (nbits + 7) >> 3;
+    if (bits == nullptr) {
+        bit0 = 0;
+        nbytes = 0;
+    } else if (!dev) { // only the bytes that hold bits bit0 .. bit0 + ntotal - 1 travel
+        const int64_t b0 = sel_bit0 >> 3, b1 = (sel_bit0 + ix->ntotal + 7) >> 3;
+        int rc = ix->sel_raw.ensure((size_t)(b1 - b0));
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ix->sel_raw.p, bits + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, st));
+        src = (const uint8_t*)ix->sel_raw.p;
+        bit0 = sel_bit0 & 7;
+        nbytes = b1 - b0;
+    }
+    return MIPS_OK;
+}
+
 int stage_selector(mips_index* ix, Selector& sel, int64_t nq, hipStream_t st) {
     const int64_t ntiles = (ix->ntotal + mips::TM - 1) / mips::TM;
     const int64_t nwords = ntiles * (mips::TM / 32);
     int rc = ix->sel_words.ensure(16 + (size_t)nwords * sizeof(unsigned));
     if (rc) return rc;
-    const uint8_t* src = sel.bits;
-    int64_t bit0 = sel.bit0;
-    int64_t nbytes = (sel.nbits + 7) >> 3;
-    if (sel.bits == nullptr) {
-        bit0 = 0;
-        nbytes = 0;
-    } else if (!sel.dev) { // only the bytes that hold bits bit0 .. bit0 + ntotal - 1 travel
-        const int64_t b0 = sel.bit0 >> 3, b1 = (sel.bit0 + ix->ntotal + 7) >> 3;
-        rc = ix->sel_raw.ensure((size_t)(b1 - b0));
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ix->sel_raw.p, sel.bits + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, st));
-        src = (const uint8_t*)ix->sel_raw.p;
-        bit0 = sel.bit0 & 7;
-        nbytes = b1 - b0;
-    }
+    const uint8_t* src;
+    int64_t bit0, nbytes;
+    rc = bitmap_on_device(ix, sel.bits, sel.nbits, sel.bit0, sel.dev, st, src, bit0, nbytes);
+    if (rc) return rc;
     unsigned long long* nsel = (unsigned long long*)ix->sel_words.p;
     unsigned* words = (unsigned*)((unsigned char*)ix->sel_words.p + 16);
     HIP_TRY(hipMemsetAsync(nsel, 0, 16, st));

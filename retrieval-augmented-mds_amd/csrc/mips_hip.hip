@@ -16,6 +16,7 @@
 
 #include "../../include/mips_hip.h"
 #include "../../include/mips_hip_sharded.h"
+#include "../../include/mips_hip_update.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -30,6 +31,7 @@
 #include "range_kernels.hpp"
 #include "range_merge_kernels.hpp"
 #include "select_kernels.hpp"
+#include "remove_kernels.hpp"
 
 #include "host_state.hpp"
 #include "host_launch.hpp"
@@ -37,6 +39,8 @@
 #include "host_wide.hpp"
 #include "host_range.hpp"
 #include "host_range_merge.hpp"
+#include "remove_plan.hpp"
+#include "host_remove.hpp"
 
 extern "C" {
 
@@ -828,6 +832,21 @@ int mips_range_merge_records(const int64_t* gathered, int parts, int64_t nq, int
     return range_merge_records(gathered, parts, nq, stride, out_lims, out_scores, out_idx, cap, workspace, device, (hipStream_t)hip_stream);
 }
 
+int mips_index_remove(mips_index_t* ix, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, int flags, int64_t out_counts[2],
+                      void* hip_stream) {
+    if (!ix || !out_counts) return fail(MIPS_E_INVALID, "mips_index_remove: index or out_counts is NULL");
+    if (sel_bit0 < 0 || sel_nbits < 0 || sel_bit0 > sel_nbits || ix->ntotal > sel_nbits - sel_bit0)
+        return fail(MIPS_E_INVALID, "mips_index_remove: the bitmap's %lld bits from bit %lld on do not cover the index's %lld rows",
+                    (long long)sel_nbits, (long long)sel_bit0, (long long)ix->ntotal);
+    if (!sel_bits && ix->ntotal > 0) return fail(MIPS_E_INVALID, "mips_index_remove: the bitmap is NULL");
+    DeviceGuard g(ix->device);
+    const int prev = take_scan_error(ix, "mips_index_remove");
+    if (prev) return prev;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st);
+    return index_remove(ix, sel_bits, sel_nbits, sel_bit0, (flags & MIPS_SEL_DEVICE) != 0, out_counts, st);
+}
+
 int mips_filter_ignore(const float* scores, const int64_t* idx, const int64_t* ignore, int64_t nq, int k_fetched, int k,
                        float* out_s, int64_t* out_i, int device, void* hip_stream) {
     if (nq < 0 || k < 0 || k_fetched < k) return fail(MIPS_E_INVALID, "mips_filter_ignore: bad sizes");
@@ -961,6 +980,10 @@ int mips_index_set_param(mips_index_t* ix, const char* name, int64_t value) {
     } else if (n == "resolve_budget") {
         if (value < 0) return fail(MIPS_E_INVALID, "mips_index_set_param: resolve_budget must be >= 0");
         ix->resolve_budget = (int)std::min<int64_t>(value, mips::RESOLVE_MAX);
+    } else if (n == "remove_window_rows") {
+        if (value < 0 || value % mips::REM_TILE != 0 || value > (1ll << 30))
+            return fail(MIPS_E_INVALID, "mips_index_set_param: remove_window_rows must be a multiple of %d (0 = automatic)", mips::REM_TILE);
+        ix->opt_remove_window = value;
     } else if (n == "spin_limit") ix->opt_spin_limit = (int)std::max<int64_t>(-1, std::min<int64_t>(value, 1 << 30));
     else if (n == "sub") {
         if (value != 0)

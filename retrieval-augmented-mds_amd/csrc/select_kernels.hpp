@@ -18,25 +18,31 @@ constexpr int SEL_THREADS = 256;
 
 // bits: the caller's bytes, nbytes of them (bytes past that are never read); bit0 >= 0 and bit0 + ntotal <= 8 * nbytes;
 // or nullptr: all rows selected
+// word w of the staged form (shared with the removal's staging, remove_kernels.hpp)
+__device__ inline unsigned selector_word(const uint8_t* bits, int64_t nbytes, int64_t bit0, int64_t ntotal, int64_t w) {
+    const int64_t left = ntotal - 32 * w; // rows of this word that exist
+    unsigned v = 0u;
+    if (left > 0) {
+        const int64_t b = bit0 + 32 * w;
+        const int64_t byte0 = b >> 3;
+        const int sh = (int)(b & 7);
+        unsigned long long acc = bits == nullptr ? ~0ull : 0ull;
+        if (bits != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 5; ++i)
+                if (byte0 + i < nbytes) acc |= (unsigned long long)bits[byte0 + i] << (8 * i);
+        }
+        v = (unsigned)(acc >> sh);
+        if (left < 32) v &= (1u << (int)left) - 1u;
+    }
+    return v;
+}
+
 __global__ __launch_bounds__(SEL_THREADS) void selector_stage_kernel(const uint8_t* bits, int64_t nbytes, int64_t bit0, int64_t ntotal,
                                                                      unsigned* words, int64_t nwords, unsigned long long* nsel) {
     unsigned long long mine = 0ull;
     for (int64_t w = (int64_t)blockIdx.x * SEL_THREADS + threadIdx.x; w < nwords; w += (int64_t)gridDim.x * SEL_THREADS) {
-        const int64_t left = ntotal - 32 * w; // rows of this word that exist
-        unsigned v = 0u;
-        if (left > 0) {
-            const int64_t b = bit0 + 32 * w;
-            const int64_t byte0 = b >> 3;
-            const int sh = (int)(b & 7);
-            unsigned long long acc = bits == nullptr ? ~0ull : 0ull;
-            if (bits != nullptr) {
-#pragma unroll
-                for (int i = 0; i < 5; ++i)
-                    if (byte0 + i < nbytes) acc |= (unsigned long long)bits[byte0 + i] << (8 * i);
-            }
-            v = (unsigned)(acc >> sh);
-            if (left < 32) v &= (1u << (int)left) - 1u;
-        }
+        const unsigned v = selector_word(bits, nbytes, bit0, ntotal, w);
         words[w] = v;
         mine += (unsigned long long)__popc(v);
     }

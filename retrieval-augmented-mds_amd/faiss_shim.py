@@ -136,6 +136,14 @@ def _selector_of(params, ntotal: int):
     return sel.bitmap(ntotal) if isinstance(sel, IDSelector) else sel
 
 
+def removal_mask(sel, ntotal: int) -> np.ndarray:
+    """What IndexFlat.remove_ids takes (an IDSelector, or ids as faiss's IDSelectorBatch reads them) -> bool [ntotal], True = the
+    row leaves.  Ids the index does not hold remove nothing, as in faiss."""
+    if not isinstance(sel, IDSelector):
+        sel = IDSelectorBatch(sel)
+    return np.ascontiguousarray(sel.mask(int(ntotal)), dtype=np.bool_)
+
+
 def _no_other_keywords(what: str, kwargs: dict) -> None:
     if kwargs:
         raise TypeError(f"{what}() got an unexpected keyword argument {sorted(kwargs)[0]!r} (params= is the one it takes)")
@@ -143,7 +151,7 @@ def _no_other_keywords(what: str, kwargs: dict) -> None:
 
 class IndexFlat:
     """faiss.IndexFlat(d, metric): d, ntotal, metric_type, is_trained, verbose, nprobe, add / train / search / range_search /
-    reset."""
+    reset / remove_ids."""
 
     is_trained = True
 
@@ -184,6 +192,14 @@ class IndexFlat:
     def reset(self) -> None:
         if self._inner is not None:
             self._inner.reset()
+
+    def remove_ids(self, sel) -> int:
+        """faiss Index.remove_ids(sel) -> the number of rows removed: any IDSelector of this module, or an int64 array of ids
+        (faiss wraps it into an IDSelectorBatch).  The surviving rows keep their order and are renumbered, as in
+        faiss.IndexFlat.  L2: phi follows the stored rows, so the index equals one built from the surviving rows."""
+        if self._inner is None or self._inner.ntotal == 0:
+            return 0
+        return self._inner.remove_ids(np.packbits(removal_mask(sel, self._inner.ntotal), bitorder="little"))
 
     def add(self, x) -> None:
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -181,6 +181,27 @@ class MipsIndex:
         _lib.check(self._lib.mips_index_reset(self._h), "mips_index_reset")
         self._nlabelled = 0
 
+    def remove_ids(self, sel, sel_bit0: int = 0) -> int:
+        """faiss IndexFlat.remove_ids: take the selected rows out, in place (mips_index_remove).  The surviving rows keep their
+        order and are renumbered 0 .. ntotal - 1; labels follow their rows; phi and the row-norm maxima follow the stored rows
+        (a set_phi override stays).  sel: a Selector, a bool mask, a NumPy or torch uint8 bitmap, or an integer array / tensor
+        of row ids (duplicates allowed); bit sel_bit0 + i of a bitmap or mask decides local row i, ids count from sel_bit0 too.
+        SYNCHRONISES the current stream once.  -> the number of rows removed."""
+        from .selector import Selector, is_id_list
+
+        sel_bit0 = int(sel_bit0)
+        is_ids = is_id_list(sel)
+        with self._mutex:
+            if is_ids:
+                sel = Selector.from_ids(sel, sel_bit0 + self.ntotal, device=self.device)
+            ptr, nbits, flag, keep = self._sel_args(sel, sel_bit0, "remove_ids")
+            counts = (ctypes.c_int64 * 2)()
+            _lib.check(self._lib.mips_index_remove(self._h, ptr, nbits, sel_bit0, flag, counts, _stream_handle(self.device)),
+                       "mips_index_remove")
+            self._nlabelled = int(counts[1])
+        del keep
+        return int(counts[0])
+
     def set_labels(self, labels, row0: int = 0) -> None:
         """One int32 group label per row for rows [row0, row0 + len(labels)) (NumPy or torch int array, host or CUDA): what
         groups= of search_wide / range_search tests.  The labelled rows are a prefix of the index -- row0 may not lie behind

@@ -342,6 +342,41 @@ class KnowledgeBase:
         order = np.lexsort((j, i))
         return i[order], j[order], s[order]
 
+    def remove_rows(self, rows) -> int:
+        """Drops the listed rows (int ids, duplicates allowed) from every column and from every attached index
+        (remove_ids_global on a row-sharded index, remove_ids otherwise): the surviving rows keep their order and are
+        renumbered.  Group labels travel with their rows inside the index; the code table of set_groups stays as it is (a value
+        whose last row left keeps its code, which no row carries any more).  -> the number of rows dropped."""
+        n = len(self)
+        ids = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+        if ids.size and (ids[0] < 0 or ids[-1] >= n):
+            raise ValueError(f"remove_rows: a row lies outside [0, {n})")
+        if ids.size == 0:
+            return 0
+        keep = np.ones(n, dtype=np.bool_)
+        keep[ids] = False
+        for name, holder in self._indexes.items():
+            index = holder.faiss_index
+            if index.ntotal != n:
+                raise ValueError(f"remove_rows: index {name!r} holds {index.ntotal} rows, the columns {n}")
+            if not (hasattr(index, "remove_ids_global") or hasattr(index, "remove_ids")):
+                raise ValueError(f"remove_rows: index {name!r} cannot remove rows")
+        for holder in self._indexes.values():
+            index = holder.faiss_index
+            (index.remove_ids_global if hasattr(index, "remove_ids_global") else index.remove_ids)(ids)
+        for c, v in list(self.columns.items()):
+            self.columns[c] = v[keep] if isinstance(v, np.ndarray) else [e for e, k in zip(v, keep) if k]
+        return int(ids.size)
+
+    def drop_near_duplicates(self, index_name: str, threshold: float, batch_rows: int = 4096) -> np.ndarray:
+        """Removes every row that has a LOWER-numbered near duplicate -- the j of the (i, j) pairs of near_duplicates, so the
+        first row of every cluster stays -- from the columns and every index (remove_rows).  -> the removed row numbers as they
+        were before the removal (int64, ascending)."""
+        _, j, _ = self.near_duplicates(index_name, threshold, batch_rows=batch_rows)
+        gone = np.unique(j)
+        self.remove_rows(gone)
+        return gone
+
     def get_nearest_examples_batch(self, index_name: str, queries, k: int = 10, selector=None, groups=None, group_mode: str = "exclude"):
         """HF Dataset.get_nearest_examples_batch as used at retriever_lightning.py:317-321: returns (scores
         per query, examples per query as dict of columns); ids < 0 are dropped like datasets/search.py does.

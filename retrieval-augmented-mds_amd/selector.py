@@ -10,6 +10,17 @@ from __future__ import annotations
 import numpy as np
 
 
+def is_id_list(sel) -> bool:
+    """Does `sel` list row ids (an integer array, tensor or sequence) rather than flag rows (bool mask, uint8 bitmap)?"""
+    import torch
+
+    if isinstance(sel, torch.Tensor):
+        return sel.dtype not in (torch.bool, torch.uint8) and not sel.dtype.is_floating_point
+    if isinstance(sel, np.ndarray):
+        return sel.dtype.kind in "iu" and sel.dtype != np.uint8
+    return isinstance(sel, (list, tuple)) and (len(sel) == 0 or not isinstance(sel[0], (bool, np.bool_)))
+
+
 class Selector:
     def __init__(self, bits, nbits: int):
         """bits: uint8 tensor of (nbits + 7) // 8 bytes whose bits at and past nbits are clear (use the from_* constructors)."""

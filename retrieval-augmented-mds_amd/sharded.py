@@ -31,6 +31,16 @@ def shard_bounds(n: int, world: int, rank: int):
     return lo, hi
 
 
+def shard_offsets(counts, rank: int):
+    """Row ranges of shards that hold counts[r] rows each, laid end to end in rank order: -> (lo, hi, total) of `rank`.  What
+    the shards of an index are after remove_ids_global (shard_bounds describes them only until then)."""
+    counts = [int(c) for c in counts]
+    if any(c < 0 for c in counts) or not 0 <= int(rank) < len(counts):
+        raise ValueError(f"shard_offsets: rank {rank} of counts {counts}")
+    lo = sum(counts[:int(rank)])
+    return lo, lo + counts[int(rank)], sum(counts)
+
+
 def pack_topk(scores, idx):
     """(float32 [nq,k], int64 [nq,k]) torch tensors -> int64 [nq,k,2]."""
     import torch
@@ -85,6 +95,7 @@ class ShardedMipsIndex:
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.ntotal_global = 0
         self.lo = self.hi = 0
+        self._even = True  # the shards are shard_bounds(ntotal_global, ...): until remove_ids_global
         self.local = None
         self._local_range_search = local_range_search
         self._range_merge = range_merge
@@ -109,6 +120,7 @@ class ShardedMipsIndex:
 
     def add_global(self, x) -> None:
         """Every rank sees the full [N, d] array (NumPy / memmap / torch) and keeps its own rows."""
+        self._refuse_after_removal("add_global")
         lo, hi = self.set_global_size(len(x))
         if self.local is not None and hi > lo:
             self.local.reserve(hi - lo)
@@ -116,11 +128,52 @@ class ShardedMipsIndex:
         self._sync_phi()
 
     def add_synthetic_global(self, n: int, seed: int, kind: int) -> None:
+        self._refuse_after_removal("add_synthetic_global")
         lo, hi = self.set_global_size(n)
         if hi > lo:
             self.local.reserve(hi - lo)
             self.local.add_synthetic(hi - lo, row0=lo, seed=seed, kind=kind)
         self._sync_phi()
+
+    def _refuse_after_removal(self, what: str) -> None:
+        if not self._even:
+            raise ValueError(f"{what}: remove_ids_global left shards of unequal size (rows [{self.lo}, {self.hi}) here), and this "
+                             "call places rows by the even partition shard_bounds(); save() and load() the index to re-partition it")
+
+    def remove_ids_global(self, sel) -> int:
+        """COLLECTIVE MipsIndex.remove_ids: every rank passes the same GLOBAL selector (Selector, bool mask, uint8 bitmap; one
+        bit per global row) or the same global row ids; each shard removes its own rows (its bits start at `lo`), ONE small
+        all-gather of the shards' new sizes renumbers the shards (shard_offsets), and an L2 index agrees on the new phi.
+        Searches, selectors and save() go on working with the new lo / hi; the shards are no longer the even partition, so
+        add_global is refused from here on.  -> the number of rows removed from the whole index."""
+        import torch
+        import torch.distributed as dist
+
+        from .selector import Selector, is_id_list
+
+        if self.local is None:
+            raise ValueError("remove_ids_global needs the library's own local index (injected steps hold no rows)")
+        if is_id_list(sel):
+            sel = Selector.from_ids(sel, self.ntotal_global, device=self.local.device)
+        nbits = sel.nbits if isinstance(sel, Selector) else (
+            8 * sel.numel() if isinstance(sel, torch.Tensor) and sel.dtype == torch.uint8 else
+            8 * sel.size if isinstance(sel, np.ndarray) and sel.dtype == np.uint8 else len(sel))
+        if nbits < self.ntotal_global:
+            raise ValueError(f"remove_ids_global: the selector has {nbits} bits, the sharded index {self.ntotal_global} rows")
+        before = self.ntotal_global
+        self.local.remove_ids(sel, sel_bit0=self.lo)
+        counts = [self.local.ntotal]
+        if self.world > 1:
+            nccl = dist.get_backend(self.group) == "nccl"
+            mine = torch.tensor(counts, dtype=torch.int64, device=f"cuda:{self.local.device}" if nccl else "cpu")
+            every = torch.empty(self.world, dtype=torch.int64, device=mine.device)
+            dist.all_gather_into_tensor(every, mine, group=self.group)
+            counts = every.tolist()
+        self.lo, self.hi, self.ntotal_global = shard_offsets(counts, self.rank)
+        if self.ntotal_global != before:
+            self._even = False
+        self._sync_phi()
+        return before - self.ntotal_global
 
     def set_labels_global(self, labels) -> None:
         """Every rank sees the full [N] int array of row labels (MipsIndex.set_labels) and keeps those of its own rows."""
