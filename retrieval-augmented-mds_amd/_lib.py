@@ -20,12 +20,14 @@ LIB_PATH = os.path.join(LIB_DIR, "libmips_hip.so")
 HEADER = os.path.join(_ROOT, "include", "mips_hip.h")
 HEADER_SHARDED = os.path.join(_ROOT, "include", "mips_hip_sharded.h")  # helpers of the shard exchange (no index handle)
 HEADER_UPDATE = os.path.join(_ROOT, "include", "mips_hip_update.h")  # calls that change the rows an index holds
+HEADER_ROWS = os.path.join(_ROOT, "include", "mips_hip_rows.h")  # stored rows, labels and scores by row id
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
 DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3, DTYPE_FP8_E4M3_DOCS = 0, 1, 2, 3
 METRIC_IP, METRIC_L2 = 0, 1
 Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP, SEL_DEVICE, GRP_DEVICE = 1, 2, 4, 8, 16, 32
+IDS_DEVICE, ROWS_ZERO_MISSING = 64, 128  # include/mips_hip_rows.h
 GRP_EXCLUDE, GRP_ONLY = 0, 1  # MIPS_GRP_*: the mode of a grouped search
 LABEL_NONE = -(1 << 31)  # MIPS_LABEL_NONE = INT32_MIN: a query that is not group-filtered
 SYNTH_LATTICE, SYNTH_GAUSS, SYNTH_LATTICE_FP8 = 0, 1, 2
@@ -39,7 +41,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -142,7 +144,12 @@ def _bind(lib):
     sig_update = {  # include/mips_hip_update.h
         "mips_index_remove": (i32, [vp, vp, i64, i64, i32, c.POINTER(i64), vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded, **sig_update}.items():
+    sig_rows = {  # include/mips_hip_rows.h
+        "mips_index_reconstruct": (i32, [vp, vp, i64, i64, vp, i32, i64, i32, vp]),
+        "mips_index_gather_labels": (i32, [vp, vp, i64, i64, vp, i32, vp]),
+        "mips_score_subset": (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i32, vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -163,6 +170,7 @@ EXPORTS = (
 
 EXPORTS_SHARDED = ("mips_range_merge_records",)  # what include/mips_hip_sharded.h declares; the same library exports it
 EXPORTS_UPDATE = ("mips_index_remove",)  # what include/mips_hip_update.h declares; the same library exports it
+EXPORTS_ROWS = ("mips_index_reconstruct", "mips_index_gather_labels", "mips_score_subset")  # include/mips_hip_rows.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:

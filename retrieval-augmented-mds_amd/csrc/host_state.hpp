@@ -136,6 +136,8 @@ struct mips_index {
     // row removal (mips_index_remove, host_remove.hpp; it stages into sel_raw / sel_words): "remove_window_rows", rows a gather
     // launch compacts (a multiple of 128; 0 = automatic, host_remove.hpp)
     int64_t opt_remove_window = 0;
+    // rows by id (include/mips_hip_rows.h, host_rows.hpp): the device copy of host ids, and the device result of a host-output call
+    Buffer row_ids, row_out;
     // grouped searches (mips_search_wide_grp / mips_range_search_grp): one int32 label per row in storage of its own, allocated in
     // whole 128-row tiles for at least `capacity` rows (mips_index_set_labels grows it and keeps what it held, so it survives the
     // growth of the rows); rows [0, nlabelled) carry a label.  grp_q: the staged per-query labels of the call in flight.

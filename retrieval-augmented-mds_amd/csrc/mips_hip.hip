@@ -17,6 +17,7 @@
 #include "../../include/mips_hip.h"
 #include "../../include/mips_hip_sharded.h"
 #include "../../include/mips_hip_update.h"
+#include "../../include/mips_hip_rows.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -32,6 +33,7 @@
 #include "range_merge_kernels.hpp"
 #include "select_kernels.hpp"
 #include "remove_kernels.hpp"
+#include "rows_kernels.hpp"
 
 #include "host_state.hpp"
 #include "host_launch.hpp"
@@ -41,6 +43,7 @@
 #include "host_range_merge.hpp"
 #include "remove_plan.hpp"
 #include "host_remove.hpp"
+#include "host_rows.hpp"
 
 extern "C" {
 
@@ -159,6 +162,8 @@ int mips_index_destroy(mips_index_t* ix) {
     ix->sel_raw.release();
     ix->sel_words.release();
     ix->grp_q.release();
+    ix->row_ids.release();
+    ix->row_out.release();
     if (ix->labels) (void)hipFree(ix->labels);
     for (int e = 0; e < mips_index::kEvRing; ++e) {
         if (ix->ev0[e]) (void)hipEventDestroy(ix->ev0[e]);
@@ -845,6 +850,50 @@ int mips_index_remove(mips_index_t* ix, const uint8_t* sel_bits, int64_t sel_nbi
     const hipStream_t st = (hipStream_t)hip_stream;
     ORDER_ON(ix, st);
     return index_remove(ix, sel_bits, sel_nbits, sel_bit0, (flags & MIPS_SEL_DEVICE) != 0, out_counts, st);
+}
+
+// ---- include/mips_hip_rows.h
+int mips_index_reconstruct(mips_index_t* ix, const int64_t* ids, int64_t n, int64_t idx_offset, void* out, int out_dtype, int64_t out_ld,
+                           int flags, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "mips_index_reconstruct: index is NULL");
+    if (n < 0 || out_ld < ix->d) return fail(MIPS_E_INVALID, "mips_index_reconstruct: n = %lld, out_ld = %lld for rows of %lld columns", (long long)n,
+                                             (long long)out_ld, (long long)ix->d);
+    const int raw_dtype = ix->plane > 0 ? MIPS_DTYPE_F32 : ix->esize == 2 ? MIPS_DTYPE_BF16 : MIPS_DTYPE_FP8_E4M3;
+    if (out_dtype != MIPS_DTYPE_F32 && out_dtype != raw_dtype)
+        return fail(MIPS_E_INVALID, "mips_index_reconstruct: out_dtype must be F32 (decoded) or the storage's element type %d (raw), got %d", raw_dtype,
+                    out_dtype);
+    if (n == 0) return MIPS_OK;
+    if (!ids || !out) return fail(MIPS_E_INVALID, "mips_index_reconstruct: NULL buffer");
+    DeviceGuard g(ix->device);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st);
+    return index_reconstruct(ix, ids, n, idx_offset, out, out_dtype, out_ld, flags, st);
+}
+
+int mips_index_gather_labels(mips_index_t* ix, const int64_t* ids, int64_t n, int64_t idx_offset, int32_t* out, int flags, void* hip_stream) {
+    if (!ix || n < 0) return fail(MIPS_E_INVALID, "mips_index_gather_labels: bad argument");
+    if (n == 0) return MIPS_OK;
+    if (!ids || !out) return fail(MIPS_E_INVALID, "mips_index_gather_labels: NULL buffer");
+    DeviceGuard g(ix->device);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st);
+    return index_gather_labels(ix, ids, n, idx_offset, out, flags, st);
+}
+
+int mips_score_subset(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, const int64_t* ids, int k, float* out_scores, int64_t idx_offset,
+                      int flags, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "mips_score_subset: index is NULL");
+    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_score_subset: negative nq or k");
+    if (!src_dtype_ok(ix, q_dtype, true)) return fail(MIPS_E_INVALID, "mips_score_subset: q_dtype must be F32 or BF16 (or FP8_E4M3 bytes for an all-e4m3 index)");
+    if (nq == 0 || k == 0) return MIPS_OK;
+    if (!q || !ids || !out_scores) return fail(MIPS_E_INVALID, "mips_score_subset: NULL buffer");
+    if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_score_subset: more than 2^24 queries in one call");
+    DeviceGuard g(ix->device);
+    const int prev = take_scan_error(ix, "mips_score_subset"); // (the call rewrites the searches' staged queries)
+    if (prev) return prev;
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st);
+    return index_score_subset(ix, q, q_dtype, nq, ids, k, out_scores, idx_offset, flags, st);
 }
 
 int mips_filter_ignore(const float* scores, const int64_t* idx, const int64_t* ignore, int64_t nq, int k_fetched, int k,

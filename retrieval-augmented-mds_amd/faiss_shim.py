@@ -151,7 +151,7 @@ def _no_other_keywords(what: str, kwargs: dict) -> None:
 
 class IndexFlat:
     """faiss.IndexFlat(d, metric): d, ntotal, metric_type, is_trained, verbose, nprobe, add / train / search / range_search /
-    reset / remove_ids."""
+    reset / remove_ids / reconstruct / reconstruct_n / reconstruct_batch / search_and_reconstruct / compute_distance_subset."""
 
     is_trained = True
 
@@ -255,6 +255,81 @@ class IndexFlat:
         sel = _selector_of(params, ix.ntotal)
         lims, D, I = ix.range_search(q, thresh) if sel is None else ix.range_search(q, thresh, selector=sel)
         return (np.asarray(lims).astype(np.uint64), np.ascontiguousarray(D, dtype=np.float32), np.ascontiguousarray(I, dtype=np.int64))
+
+    # ---- rows by id.  L2: the index stores the un-augmented d - 1 columns; the augmentation column of a row handed back is
+    # RECOMPUTED from the stored values (l2_augmentation_column), not stored -- it equals the column that was added up to the
+    # storage's rounding of the other columns and float32 rounding of the square root.
+    def _rows_out(self, rows: np.ndarray) -> np.ndarray:
+        if self.metric_type != METRIC_L2:
+            return rows
+        flat = rows.reshape(-1, rows.shape[-1])
+        col = l2_augmentation_column(flat, self._inner.phi() if flat.shape[0] else 0.0)
+        return np.concatenate((flat, col[:, None]), axis=1).reshape(rows.shape[:-1] + (self.d,))
+
+    def _l2_queries(self, x, what: str) -> np.ndarray:
+        q = np.ascontiguousarray(x, dtype=np.float32)
+        if self.metric_type == METRIC_L2:
+            if q.ndim != 2 or q.shape[1] != self.d:
+                raise ValueError(f"{what}: expected [nq, {self.d}], got {q.shape}")
+            if np.any(q[:, -1] != 0):
+                raise ValueError(f"L2 {what}: the queries' last (augmentation) column is not zero; this index answers queries "
+                                 "prepared by augment_xq (sotasum/mips.py:68-70)")
+            q = np.ascontiguousarray(q[:, :-1])
+        return q
+
+    def reconstruct(self, key: int) -> np.ndarray:
+        """faiss Index.reconstruct(key) -> float32 [d]; IndexError outside [0, ntotal) (an empty index: always)."""
+        key = int(key)
+        if not 0 <= key < self.ntotal:
+            raise IndexError(f"reconstruct: row {key} of an index of {self.ntotal}")
+        return self._rows_out(self._inner.reconstruct(key))
+
+    def reconstruct_n(self, n0: int = 0, ni: int = -1) -> np.ndarray:
+        """faiss Index.reconstruct_n(n0, ni) -> float32 [ni, d]; ni = -1 (or None): up to the last row."""
+        n0 = int(n0)
+        ni = self.ntotal - n0 if ni is None or int(ni) < 0 else int(ni)
+        if n0 < 0 or ni < 0 or n0 + ni > self.ntotal:
+            raise IndexError(f"reconstruct_n: rows [{n0}, {n0 + ni}) of an index of {self.ntotal}")
+        if ni == 0:
+            return np.empty((0, self.d), dtype=np.float32)
+        return self._rows_out(self._inner.reconstruct_n(n0, ni))
+
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """faiss Index.reconstruct_batch(ids) -> float32 [..., d] for int64 ids [...]; negative ids (the -1 padding of a search)
+        give NaN rows, an id >= ntotal raises IndexError."""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if ids.size and int(ids.max()) >= self.ntotal:
+            raise IndexError(f"reconstruct_batch: id {int(ids.max())} of an index of {self.ntotal}")
+        if ids.size == 0 or self._inner is None:
+            return np.full(ids.shape + (self.d,), np.nan, dtype=np.float32)
+        return self._rows_out(self._inner.reconstruct_batch(ids))
+
+    def search_and_reconstruct(self, x, k: int, params=None, **kwargs):
+        """faiss Index.search_and_reconstruct(x, k) -> (D, I, R float32 [nq, k, d]): search(x, k, params) and the rows of I; the
+        rows of the -1 slots are NaN."""
+        _no_other_keywords("search_and_reconstruct", kwargs)
+        D, I = self.search(x, k, params=params)
+        return D, I, self.reconstruct_batch(I)
+
+    def compute_distance_subset(self, x, labels) -> np.ndarray:
+        """faiss Index.compute_distance_subset, spelled for NumPy (the SWIG pointer form cannot be taken): x float32 [nq, d],
+        labels int64 [nq, k] -> D float32 [nq, k], the index's own score of every pair (what search returns for it); negative
+        labels give -inf (L2: +inf)."""
+        q = self._l2_queries(x, "compute_distance_subset")
+        labels = np.ascontiguousarray(labels, dtype=np.int64)
+        if labels.ndim != 2 or labels.shape[0] != q.shape[0]:
+            raise ValueError(f"compute_distance_subset: expected labels [{q.shape[0]}, k], got {labels.shape}")
+        if labels.size and int(labels.max()) >= self.ntotal:
+            raise IndexError(f"compute_distance_subset: id {int(labels.max())} of an index of {self.ntotal}")
+        return self._index().compute_distance_subset(q, labels)
+
+
+def l2_augmentation_column(rows: np.ndarray, phi: float) -> np.ndarray:
+    """The last column of the phi-augmented form of `rows` (float32 [n, d - 1], as stored): float32(sqrt(max(phi - sum x^2, 0)))
+    with the sum taken sequentially in fp64 over the columns (augment_xb, sotasum/mips.py:59-65).  NaN rows stay NaN."""
+    x = np.asarray(rows, dtype=np.float64)
+    sq = np.cumsum(x * x, axis=1)[:, -1] if x.shape[1] else np.zeros(x.shape[0])
+    return np.sqrt(np.maximum(float(phi) - sq, 0.0)).astype(np.float32)
 
 
 class IndexFlatIP(IndexFlat):

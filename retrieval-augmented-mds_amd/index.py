@@ -276,6 +276,141 @@ class MipsIndex:
                                                   _stream_handle(self.device)), "mips_index_read_rows")
         return out
 
+    # ------------------------------------------------------------------ rows by id (include/mips_hip_rows.h)
+    _RAW_NP = {_lib.DTYPE_BF16: np.uint16, _lib.DTYPE_FP8_E4M3: np.uint8, _lib.DTYPE_FP8_E4M3_DOCS: np.uint8, _lib.DTYPE_F32: np.float32}
+
+    def _ids_arg(self, ids, what: str):
+        """ids of any shape (NumPy / sequence -> host, CUDA tensor -> device) -> (pointer, shape, is_device, keepalive)."""
+        import torch
+
+        if isinstance(ids, torch.Tensor):
+            if ids.dtype.is_floating_point or ids.dtype.is_complex or ids.dtype == torch.bool:
+                raise ValueError(f"{what}: expected integer ids, got {ids.dtype}")
+            if ids.is_cuda:
+                if ids.device.index != self.device:
+                    ids = ids.to(f"cuda:{self.device}")
+                t = ids.to(torch.int64).contiguous()
+                return t.data_ptr(), tuple(t.shape), True, t
+            ids = ids.numpy()
+        a = np.asarray(ids)
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError(f"{what}: expected integer ids, got {a.dtype}")
+        if a.size and a.dtype.kind == "u" and int(a.max()) > np.iinfo(np.int64).max:
+            raise ValueError(f"{what}: id {int(a.max())} does not fit int64")   # (the cast below would make it negative: "no row")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        return a.ctypes.data, a.shape, False, a
+
+    def reconstruct_batch(self, ids, raw: bool = False, idx_offset: int = 0, out=None, zero_missing: bool = False):
+        """The stored rows ids[...] - idx_offset -> [..., d] (faiss Index.reconstruct_batch; mips_index_reconstruct, one
+        launch).  float32: the decoded values, exactly what the searches score (an "f32" index: the float32 values it was
+        given, bit for bit); raw=True: the storage's own bits (np.uint16 / torch.bfloat16, np.uint8 / torch.uint8 e4m3 codes,
+        float32).  NumPy ids -> NumPy result; an id >= ntotal raises.  A CUDA tensor -> a CUDA tensor, stream-ordered, nothing
+        synchronises, and an id that names no row (negative, as the -1 padding of a search, or past the index) gives a NaN
+        row -- zero_missing=True: zero bytes.  out= (CUDA ids only): a caller-allocated CUDA tensor [..., d] of the result's
+        dtype whose last dimension is contiguous and whose leading dimensions collapse to one row pitch >= d (a slice of
+        wider rows); the elements between its rows are not written."""
+        import torch
+
+        ptr, shape, is_dev, keep = self._ids_arg(ids, "reconstruct_batch")
+        n = int(np.prod(shape, dtype=np.int64))
+        out_dtype = _lib.DTYPE_F32 if not raw else (_lib.DTYPE_FP8_E4M3 if self._f8 else self._code)
+        flags = _lib.ROWS_ZERO_MISSING if zero_missing else 0
+        if is_dev:
+            tdt = torch.float32 if (not raw or self._code == _lib.DTYPE_F32) else torch.uint8 if self._f8 else torch.bfloat16
+            if out is None:
+                out = torch.empty(shape + (self._d,), dtype=tdt, device=f"cuda:{self.device}")
+                out_ld = self._d
+            else:
+                if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device.index == self.device and out.dtype == tdt
+                        and tuple(out.shape) == shape + (self._d,)):
+                    raise ValueError(f"reconstruct_batch: out must be a CUDA {tdt} tensor {shape + (self._d,)} on cuda:{self.device}")
+                try:
+                    flat = out.view(n, self._d) if n else out
+                except RuntimeError:                         # the leading dimensions have no common pitch
+                    raise ValueError("reconstruct_batch: the leading dimensions of out do not collapse to one row pitch") from None
+                out_ld = int(flat.stride(0)) if n > 1 else self._d
+                if n and (flat.stride(1) != 1 or out_ld < self._d):
+                    raise ValueError("reconstruct_batch: out needs a contiguous last dimension and a row pitch >= d")
+            optr, flags = out.data_ptr(), flags | _lib.IDS_DEVICE | _lib.OUT_DEVICE
+        else:
+            if out is not None:
+                raise ValueError("reconstruct_batch: out= goes with CUDA ids")
+            out = np.empty(shape + (self._d,), dtype=self._RAW_NP[self._code] if raw else np.float32)
+            optr, out_ld = out.ctypes.data, self._d
+        with self._mutex:
+            _lib.check(self._lib.mips_index_reconstruct(self._h, ptr, n, int(idx_offset), optr, out_dtype, out_ld, flags,
+                                                        _stream_handle(self.device)), "mips_index_reconstruct")
+        del keep
+        return out
+
+    def reconstruct(self, key: int) -> np.ndarray:
+        """faiss Index.reconstruct: stored row `key` as np.float32 [d]; IndexError outside [0, ntotal)."""
+        key = int(key)
+        if not 0 <= key < self.ntotal:
+            raise IndexError(f"reconstruct: row {key} of an index of {self.ntotal}")
+        return self.reconstruct_batch(np.array([key], dtype=np.int64))[0]
+
+    def reconstruct_n(self, n0: int = 0, ni: int | None = None) -> np.ndarray:
+        """faiss Index.reconstruct_n: stored rows [n0, n0 + ni) as np.float32 [ni, d] (ni = None: up to the last row)."""
+        n0 = int(n0)
+        ni = self.ntotal - n0 if ni is None else int(ni)
+        if n0 < 0 or ni < 0 or n0 + ni > self.ntotal:
+            raise IndexError(f"reconstruct_n: rows [{n0}, {n0 + ni}) of an index of {self.ntotal}")
+        return self.reconstruct_batch(np.arange(n0, n0 + ni, dtype=np.int64))
+
+    def labels_of(self, ids, idx_offset: int = 0):
+        """The labels (set_labels) of rows ids[...] - idx_offset -> int32 [...]; LABEL_NONE for an id that names no row and for
+        rows behind the labelled prefix.  NumPy ids -> NumPy; a CUDA tensor -> a CUDA tensor, nothing synchronises."""
+        import torch
+
+        ptr, shape, is_dev, keep = self._ids_arg(ids, "labels_of")
+        n = int(np.prod(shape, dtype=np.int64))
+        if is_dev:
+            out = torch.empty(shape, dtype=torch.int32, device=f"cuda:{self.device}")
+            optr, flags = out.data_ptr(), _lib.IDS_DEVICE | _lib.OUT_DEVICE
+        else:
+            out = np.empty(shape, dtype=np.int32)
+            optr, flags = out.ctypes.data, 0
+        with self._mutex:
+            _lib.check(self._lib.mips_index_gather_labels(self._h, ptr, n, int(idx_offset), optr, flags, _stream_handle(self.device)),
+                       "mips_index_gather_labels")
+        del keep
+        return out
+
+    def compute_distance_subset(self, x, ids, force_ip: bool = False, idx_offset: int = 0):
+        """faiss Index.compute_distance_subset: out[j, t] = the canonical score of (x[j], row ids[j, t] - idx_offset), float32
+        [nq, k] in the caller's order (mips_score_subset).  The score is what the searches return -- scoring the I of a search
+        gives its D bit for bit --: the inner product, on an L2 index the distance unless force_ip.  An id that names no row
+        scores -inf (L2: +inf).  Any k, every storage.  x and ids on the host -> NumPy (an id >= ntotal raises); x a CUDA tensor
+        -> a CUDA tensor (host ids are copied over first)."""
+        import torch
+
+        ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        if is_dev and not (isinstance(ids, torch.Tensor) and ids.is_cuda):
+            ids = torch.as_tensor(np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids), dtype=torch.int64).to(f"cuda:{self.device}")
+        iptr, shape, ids_dev, ikeep = self._ids_arg(ids, "compute_distance_subset")
+        if len(shape) != 2 or shape[0] != nq:
+            raise ValueError(f"compute_distance_subset: expected ids [{nq}, k], got {shape}")
+        k = int(shape[1])
+        flags = (_lib.FORCE_IP if force_ip else 0) | (_lib.IDS_DEVICE if ids_dev else 0)
+        if is_dev:
+            out = torch.empty((nq, k), dtype=torch.float32, device=f"cuda:{self.device}")
+            optr, flags = out.data_ptr(), flags | _lib.Q_DEVICE | _lib.OUT_DEVICE
+        else:
+            out = np.empty((nq, k), dtype=np.float32)
+            optr = out.ctypes.data
+        with self._mutex:
+            _lib.check(self._lib.mips_score_subset(self._h, ptr, code, nq, iptr, k, optr, int(idx_offset), flags,
+                                                   _stream_handle(self.device)), "mips_score_subset")
+        del keep, ikeep
+        return out
+
+    def search_and_reconstruct(self, x, k: int, **kw):
+        """faiss Index.search_and_reconstruct -> (D, I, R [nq, k, d] float32): route_search(x, k, **kw) -- selector, groups and
+        force_ip as there, k > MAX_K goes to the wide search -- and the rows of I.  The rows of the -1 slots are NaN."""
+        D, I = route_search(self, x, int(k), **kw)
+        return D, I, self.reconstruct_batch(I, idx_offset=int(kw.get("idx_offset", 0)))
+
     # ------------------------------------------------------------------ search
     def search(self, x, k: int, idx_offset: int = 0, force_ip: bool = False, tail_stream=None):
         """faiss Index.search(x, k) -> (D, I)  (sotasum/mips.py:383-386).

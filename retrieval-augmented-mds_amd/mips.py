@@ -706,13 +706,21 @@ class Mips:
             scores, indices = out_s, out_i
         return scores, indices
 
-    def search_device(self, queries, ignore_indexes=None, k: int = 10, prepare: bool = True):
+    def search_device(self, queries, ignore_indexes=None, k: int = 10, prepare: bool = True, return_rows: bool = False):
         """Device-resident form of `_prepare_query` + `search`: takes the query CLS
         vectors as a CUDA tensor [B, d] straight from the encoder -- removing the
         `.detach().cpu().float().numpy()` hop of retriever_generator.py:143 -- normalises them on the
         device when the reference would (mips.py:369-370), searches, applies the ignore filter of
         mips.py:388-398 on the device and returns CUDA (scores [B, k], indices [B, k]); nothing
-        synchronises."""
+        synchronises.  return_rows=True: (scores, indices, rows [B, k, d] float32 CUDA), the stored rows of the hits gathered
+        on the device, still without a synchronisation (NaN rows at -1 slots) -- with a frozen document encoder they are the
+        `mips_cls` of retriever_generator.py:158-172 and go straight into cosine_rescore."""
+        out = self._search_device(queries, ignore_indexes, k, prepare)
+        if not return_rows:
+            return out
+        return out[0], out[1], self._index().reconstruct_batch(out[1])
+
+    def _search_device(self, queries, ignore_indexes, k: int, prepare: bool):
         import torch
 
         from .index import filter_ignore
@@ -739,6 +747,25 @@ class Mips:
             return index.search(q, k)
         s, i = index.search(q, k + 1)
         return filter_ignore(s, i, ignore_indexes, k)
+
+    def retrieved_group_hits(self, indices, aid):
+        """The `pred` of mips.py:460-462 without the Arrow fetch: float tensor [B, k], 1.0 where retrieved row indices[j, t]
+        belongs to the group (index_column value) aid[j].  The rows' group codes are read from the index by id
+        (MipsIndex.labels_of) -- CUDA indices give a CUDA result and nothing synchronises --; -1 slots and an aid the column
+        does not contain give 0.  Ready for retriever_metrics(pred, aid_counts)."""
+        import torch
+
+        index = self._index()
+        if not isinstance(index, MipsIndex):
+            raise NotImplementedError("retrieved_group_hits reads the labels of an unsharded MipsIndex")
+        if self.index_name not in self.embeddings._groups:
+            self.embeddings.set_groups(self.index_name, self.index_column)
+        codes = self.embeddings.group_codes(self.index_name, aid, "only")  # an unknown aid: the code no row has
+        if not isinstance(indices, torch.Tensor):
+            indices = torch.as_tensor(np.asarray(indices, dtype=np.int64))
+        labels = index.labels_of(indices if indices.is_cuda else indices.numpy())
+        labels = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(labels)
+        return (labels == torch.as_tensor(codes, device=labels.device)[:, None]).float()
 
     def np_search(self, x, k: int = 2) -> tuple:
         """mips.py:527-529: exhaustive cross-check over the stored embeddings."""

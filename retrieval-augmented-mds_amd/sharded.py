@@ -81,11 +81,14 @@ class ShardedMipsIndex:
     range_merge(gathered, parts, nq, stride) -> (lims, D, I) are the two steps of range_search (defaults
     MipsIndex.range_search_into / mips_range_merge_records); kw carries force_ip, selector + sel_bit0, groups + group_mode when
     the call has them, `gathered` is a NumPy int64 array of the records end to end.  With an injected local step the record is
-    assembled on the host.
+    assembled on the host.  local_reconstruct(ids, lo) -> np.float32 [n, d] is the local step of reconstruct_batch (default
+    MipsIndex.reconstruct_batch with idx_offset = lo and zero_missing): this shard's rows of the flat int64 `ids`, zero bytes for
+    every id that names no row here.
     """
 
     def __init__(self, d: int, metric: int = _lib.METRIC_IP, dtype: str = "bf16", group=None, device=None,
-                 local_search=None, merge=None, local_search_wide=None, local_range_search=None, range_merge=None):
+                 local_search=None, merge=None, local_search_wide=None, local_range_search=None, range_merge=None,
+                 local_reconstruct=None):
         import torch.distributed as dist
 
         self.d = int(d)
@@ -99,7 +102,8 @@ class ShardedMipsIndex:
         self.local = None
         self._local_range_search = local_range_search
         self._range_merge = range_merge
-        if local_search is None and local_search_wide is None and local_range_search is None:
+        self._local_reconstruct = local_reconstruct
+        if local_search is None and local_search_wide is None and local_range_search is None and local_reconstruct is None:
             from .index import MipsIndex
 
             self.local = MipsIndex(d, metric=metric, dtype=dtype, device=device)
@@ -448,6 +452,39 @@ class ShardedMipsIndex:
             return merge_topk_sorted_packed(gathered, nq, self.world, k, metric)
         s, i = self._local_search_wide(q, k, self.lo, **({"force_ip": True} if force_ip else {}), **sel_kw)
         return self._exchange(s, i, k, metric)
+
+    # ------------------------------------------------------------------ rows by id
+    def reconstruct_batch(self, ids):
+        """COLLECTIVE MipsIndex.reconstruct_batch: every rank passes the same GLOBAL row ids [...] (NumPy -> NumPy, CUDA tensor
+        -> CUDA tensor) and gets the same float32 rows [..., d], bit for bit those of the unsharded index.  Each shard gathers
+        the rows it holds and leaves zero bytes elsewhere (idx_offset = lo, zero_missing), ONE all-reduce (SUM) of the buffers
+        viewed as int32 assembles the rows -- exactly one shard contributes to a row, and an integer sum keeps its bits (a
+        float sum would turn -0.0 + 0.0 into +0.0 and quieten NaN payloads) --, and the ids that name no row of the whole index
+        become NaN rows.  Works on the uneven shards remove_ids_global leaves."""
+        import torch
+        import torch.distributed as dist
+
+        as_numpy = not isinstance(ids, torch.Tensor)
+        t_ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)) if as_numpy else ids.to(torch.int64)
+        shape = tuple(t_ids.shape)
+        flat = t_ids.reshape(-1)
+        if self._local_reconstruct is not None:
+            rows = torch.from_numpy(np.ascontiguousarray(self._local_reconstruct(flat.cpu().numpy(), self.lo), dtype=np.float32))
+        else:
+            rows = self.local.reconstruct_batch(flat.to(f"cuda:{self.local.device}"), idx_offset=self.lo, zero_missing=True)
+        home = rows.device
+        bits = rows.view(torch.int32)
+        if self.world > 1:
+            if dist.get_backend(self.group) == "gloo" and bits.is_cuda:
+                bits = bits.cpu()  # gloo moves host memory
+            dist.all_reduce(bits, op=dist.ReduceOp.SUM, group=self.group)  # the ONE collective of the call
+            bits = bits.to(home)
+        flat = flat.to(home)
+        bits[(flat < 0) | (flat >= self.ntotal_global)] = 0x7FC00000
+        out = bits.view(torch.float32).reshape(shape + (self.d,))
+        if as_numpy:
+            return out.cpu().numpy()
+        return out if out.device == ids.device else out.to(ids.device)
 
     # ------------------------------------------------------------------ range search
     @staticmethod
