@@ -4,7 +4,7 @@
 // in three steps with a plain struct between them: choose_scan (no HIP calls: kernel row, tiles, lists, splits, XCD groups, grid),
 // launch_scan (the ONE place that launches a scan kernel) and launch_tail (merge_select -> rescore_rank with the margin check).
 // All of them read the launch's view of the index, its staged queries and its switches from the SearchCall they are handed,
-// and write nothing on the index but scratch, statistics, the event ring and last_kernel.  DESIGN.md section 4, "Dispatch".
+// and write nothing on the index but scratch, the event ring and last_kernel.  DESIGN.md section 4, "Dispatch".
 #pragma once
 
 namespace {
@@ -143,7 +143,7 @@ const ScanInstance* generic_instance() {
 // ---- What choose_scan decides and the other two steps carry out
 struct ScanPlan {
     const ScanInstance* row; // the kernel
-    bool stationary;         // a query-stationary kernel: shares insert bounds through the class words (ix->gthr)
+    bool stationary;         // a query-stationary kernel: shares insert bounds through the class words (ix->cur.gthr)
     bool f32x;               // fp32-exact mode: generic kernel over the [hi | lo] planes, three k segments
     int tn, tm;              // queries per workgroup, documents per scheduling unit ("tile")
     int lists, list_len;     // running lists per (query, split), entries of each
@@ -404,10 +404,11 @@ inline int launch_scan(mips_index* ix, const SearchCall& c, const ScanPlan& pl, 
 }
 
 // Step 3: the tail behind the scan -- (1) K' best candidates per query by MFMA score, (2) lane-packed exact re-score + final
-// order, with the margin check's buffers.  tail_st: stream of the two launches when `split` (else the scan's own)
+// order, with the margin check's buffers.  tail_st: stream of the two launches when `split` (else the scan's own).
+// *nflag_dev: where the re-score counts the queries it flags (nullptr: the margin check is off)
 template <int KL>
 int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const mips::ScanArgs& a, int64_t nq, int k, float* d_out_s, int64_t* d_out_i,
-                int64_t* d_out_packed, int64_t idx_offset, hipStream_t st, hipStream_t tail_st, bool split) {
+                int64_t* d_out_packed, int64_t idx_offset, hipStream_t st, unsigned** nflag_dev, hipStream_t tail_st, bool split) {
     const bool f32x = pl.f32x, e8 = ix->mixed, f8 = ix->esize == 1;
     int rc;
     mips::MergeArgs m;
@@ -415,7 +416,7 @@ int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const m
     m.part_i = a.part_i;
     m.ncand = (int)pl.ncand;
     const bool f32r = f32x || c.stage1; // exact re-score on the fp32 rows (stage 1 of the two-stage search included)
-    m.docs = f32r ? (const void*)ix->rows_f32 : (const void*)c.rows;
+    m.docs = f32r ? (const void*)ix->rows_f32.p : (const void*)c.rows;
     m.qbuf = f32r ? c.qf32 : (const void*)a.qbuf;
     m.ld = c.stage1 ? c.rescore_ld : f32x ? c.plane : c.ld;
     m.k = k;
@@ -434,6 +435,7 @@ int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const m
     m.flag = nullptr;
     m.nflag = nullptr;
     m.xmax2 = ix->xmax2_dev;
+    *nflag_dev = nullptr;
     // MFMA score = fp32 accumulation of exact products (bf16 x bf16 and e4m3 x e4m3 fit fp32): |error| <= (terms) u
     // sum |q_j x_j| <= d 2^-23 |q| |x| (u = 2^-23 allows truncating adders).  fp32-exact mode scans hi.qhi + hi.qlo +
     // lo.qhi of bf16 splits: the dropped lo.qlo term adds 2^-16 |q| |x|, and there are three times the terms.
@@ -445,17 +447,17 @@ int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const m
         m.qerr2 = (const double*)ix->qerr2.p;
     }
     if (c.margin != 0) {
-        rc = ix->mbnd.ensure((size_t)nq * sizeof(float));
+        rc = ix->cur.mbnd.ensure((size_t)nq * sizeof(float));
         if (rc) return rc;
-        rc = ix->mflag.ensure((size_t)nq);
+        rc = ix->cur.mflag.ensure((size_t)nq);
         if (rc) return rc;
         rc = ensure_xmax2(ix, st);
         if (rc) return rc;
         m.xmax2 = ix->xmax2_dev;
-        m.bnd = (float*)ix->mbnd.p;
-        m.flag = (unsigned char*)ix->mflag.p;
-        m.nflag = (unsigned*)ix->gthr.p + (size_t)pl.nq_pad * 8 + 1; // zeroed with the insert bounds by the query staging
-        ix->last_nflag_dev = m.nflag;
+        m.bnd = (float*)ix->cur.mbnd.p;
+        m.flag = (unsigned char*)ix->cur.mflag.p;
+        m.nflag = (unsigned*)ix->cur.gthr.p + (size_t)pl.nq_pad * 8 + 1; // zeroed with the insert bounds by the query staging
+        *nflag_dev = m.nflag;
         if (!c.rescan) { // what the exact resolution of flagged queries starts from (resolve_kernels.hpp)
             rc = ix->keyk.ensure((size_t)nq * sizeof(float));
             if (rc) return rc;
@@ -466,9 +468,9 @@ int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const m
         }
     }
     // (1) K' best candidates per query by MFMA score, (2) lane-packed exact re-score + final order
-    rc = ix->cand.ensure((size_t)nq * KL * sizeof(int));
+    rc = ix->cur.cand.ensure((size_t)nq * KL * sizeof(int));
     if (rc) return rc;
-    int* cand = (int*)ix->cand.p;
+    int* cand = (int*)ix->cur.cand.p;
     const hipStream_t scan_st = st;
     if (split) { // the tail goes to its own stream, behind the scan
         HIP_TRY(hipEventRecord(ix->scan_done, scan_st));
@@ -489,8 +491,8 @@ int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const m
     else mips::rescore_rank_kernel<KL, mips::ElemBF16, false><<<rgrid, 64, 0, st>>>(m, cand, nq);
     HIP_TRY(hipGetLastError());
     if (split) {
-        HIP_TRY(hipEventRecord(ix->tail_done[ix->cur_set], st));
-        ix->tail_pending[ix->cur_set] = true;
+        HIP_TRY(hipEventRecord(ix->cur.tail_done, st));
+        ix->cur.tail_pending = true;
     }
     return MIPS_OK;
 }
@@ -498,13 +500,13 @@ int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const m
 // tail_st: stream of the select + exact re-score launches (nullptr or == st: the scan's own stream)
 template <int KL>
 int launch_search(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_out_s, int64_t* d_out_i, int64_t* d_out_packed,
-                  int64_t idx_offset, hipStream_t st, hipStream_t tail_st = nullptr, bool split = false) {
+                  int64_t idx_offset, hipStream_t st, unsigned** nflag_dev, hipStream_t tail_st = nullptr, bool split = false) {
     ScanPlan pl;
     int rc = choose_scan<KL>(ix, c, nq, pl);
     if (rc) return rc;
-    rc = ix->part_s.ensure((size_t)pl.nq_pad * pl.ncand * sizeof(float));
+    rc = ix->cur.part_s.ensure((size_t)pl.nq_pad * pl.ncand * sizeof(float));
     if (rc) return rc;
-    rc = ix->part_i.ensure((size_t)pl.nq_pad * pl.ncand * sizeof(int));
+    rc = ix->cur.part_i.ensure((size_t)pl.nq_pad * pl.ncand * sizeof(int));
     if (rc) return rc;
 
     mips::ScanArgs a;
@@ -523,8 +525,8 @@ int launch_search(mips_index* ix, const SearchCall& c, int64_t nq, int k, float*
     a.qgroups = pl.qgroups;
     a.qt_per_group = pl.qt_per_group;
     a.splits_per_group = pl.nsplit / (8 / pl.qgroups);
-    a.part_s = (float*)ix->part_s.p;
-    a.part_i = (int*)ix->part_i.p;
+    a.part_s = (float*)ix->cur.part_s.p;
+    a.part_i = (int*)ix->cur.part_i.p;
     a.gthr = nullptr;
     a.err = nullptr;
     a.spin_limit = ix->opt_spin_limit != 0 ? ix->opt_spin_limit : (1 << 22);
@@ -532,12 +534,12 @@ int launch_search(mips_index* ix, const SearchCall& c, int64_t nq, int k, float*
         // shared insert bounds: 8 class words per query (2 lane-half words in the older layouts) + error word
         const size_t thr_words = (size_t)pl.nq_pad * 8;
         // (allocated and cleared by mips_search together with the query staging)
-        a.gthr = (unsigned*)ix->gthr.p;
+        a.gthr = (unsigned*)ix->cur.gthr.p;
         a.err = a.gthr + thr_words;
     }
     rc = launch_scan(ix, c, pl, a, KL, st);
     if (rc) return rc;
-    return launch_tail<KL>(ix, c, pl, a, nq, k, d_out_s, d_out_i, d_out_packed, idx_offset, st, tail_st, split);
+    return launch_tail<KL>(ix, c, pl, a, nq, k, d_out_s, d_out_i, d_out_packed, idx_offset, st, nflag_dev, tail_st, split);
 }
 
 #undef MIPS_TABLE_END

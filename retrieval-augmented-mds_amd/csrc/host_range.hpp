@@ -88,27 +88,27 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
         // ---- stage the slice's queries: canonical form (bf16 rows / fp32 rows) and, fp32-exact index, bf16(q) for the scan
         const int64_t nq_padq = query_pad(ix, ns);
         const size_t row_bytes = (size_t)ix->ld * ix->qsize;
-        rc = ix->qbuf.ensure((size_t)nq_padq * row_bytes);
+        rc = ix->cur.qbuf.ensure((size_t)nq_padq * row_bytes);
         if (rc) return rc;
         if (f32x) {
-            rc = ix->qf32.ensure((size_t)nq_padq * ix->plane * sizeof(float));
+            rc = ix->cur.qf32.ensure((size_t)nq_padq * ix->plane * sizeof(float));
             if (rc) return rc;
-            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->qbuf.p, st, (float*)ix->qf32.p);
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->cur.qbuf.p, st, (float*)ix->cur.qf32.p);
             if (rc) return rc;
             rc = ix->qhi.ensure((size_t)nq_padq * ix->hp * 2);
             if (rc) return rc;
             rc = ix->qerr2.ensure((size_t)ns * sizeof(double));
             if (rc) return rc;
-            mips::convert_rows_kernel<float><<<grid_for(nq_padq * (int64_t)(ix->hp / 8), 256), 256, 0, st>>>((const float*)ix->qf32.p, ns, ix->plane,
+            mips::convert_rows_kernel<float><<<grid_for(nq_padq * (int64_t)(ix->hp / 8), 256), 256, 0, st>>>((const float*)ix->cur.qf32.p, ns, ix->plane,
                                                                                                            (uint16_t*)ix->qhi.p, ix->hp, nq_padq);
-            mips::query_resid_kernel<<<(int)((ns + 3) / 4), 256, 0, st>>>((const float*)ix->qf32.p, ns, ix->plane, (double*)ix->qerr2.p);
+            mips::query_resid_kernel<<<(int)((ns + 3) / 4), 256, 0, st>>>((const float*)ix->cur.qf32.p, ns, ix->plane, (double*)ix->qerr2.p);
             HIP_TRY(hipGetLastError());
         } else {
-            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->qbuf.p, st, nullptr, nq_padq - ns, nullptr, 0, ix->qsize);
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->cur.qbuf.p, st, nullptr, nq_padq - ns, nullptr, 0, ix->qsize);
             if (rc) return rc;
         }
-        const void* rows_c = f32x ? (const void*)ix->rows_f32 : (const void*)ix->rows;
-        const void* y_c = f32x ? (const void*)ix->qf32.p : (const void*)ix->qbuf.p;
+        const void* rows_c = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
+        const void* y_c = f32x ? (const void*)ix->cur.qf32.p : (const void*)ix->cur.qbuf.p;
 
         // ---- the thresholds of the slice, fixed from here on; empty staging, no members yet
         mips::RangeTauArgs ta;
@@ -134,8 +134,8 @@ int range_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, const f
 
         // ---- threshold scan + exact filter, chunk by chunk
         mips::WideScanArgs sa;
-        sa.docs = f32x ? (const uint16_t*)ix->rows_hi : (const uint16_t*)ix->rows;
-        sa.qbuf = f32x ? (const uint16_t*)ix->qhi.p : (const uint16_t*)ix->qbuf.p;
+        sa.docs = f32x ? (const uint16_t*)ix->rows_hi.p : (const uint16_t*)ix->rows.p;
+        sa.qbuf = f32x ? (const uint16_t*)ix->qhi.p : (const uint16_t*)ix->cur.qbuf.p;
         sa.ntotal = ix->ntotal;
         sa.ld = sld;
         sa.ksteps = sld / mips::BK;

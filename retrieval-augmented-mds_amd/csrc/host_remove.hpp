@@ -46,16 +46,13 @@ int index_remove(mips_index* ix, const uint8_t* sel_bits, int64_t sel_nbits, int
     out_counts[1] = ix->nlabelled;
     if (n == 0) return MIPS_OK;
     // a split-tail search may still re-score on the rows from its tail stream
-    for (int e = 0; e < 2; ++e)
-        if (ix->tail_pending[e]) {
-            HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[e], 0));
-            ix->tail_pending[e] = false;
-        }
+    int rc = wait_for_tail(ix, st, /*both_sets=*/true);
+    if (rc) return rc;
     const int64_t W = remove_window_rows(ix), nwin = (n + W - 1) / W;
     const int wwords = (int)(W / 32);
     // scratch: [0, 16) the labelled survivors, then one count per window, then the keep words of whole windows
     const size_t counts_bytes = (size_t)round_up(nwin * (int64_t)sizeof(int), 16);
-    int rc = ix->sel_words.ensure(16 + counts_bytes + (size_t)nwin * wwords * sizeof(unsigned));
+    rc = ix->sel_words.ensure(16 + counts_bytes + (size_t)nwin * wwords * sizeof(unsigned));
     if (rc) return rc;
     unsigned long long* lab_kept_dev = (unsigned long long*)ix->sel_words.p;
     int* kept_dev = (int*)((unsigned char*)ix->sel_words.p + 16);
@@ -93,28 +90,33 @@ int index_remove(mips_index* ix, const uint8_t* sel_bits, int64_t sel_nbits, int
     for (const mips_remove::Move& m : lab_plan.moves)
         if (!m.direct) bounce_labels = std::max(bounce_labels, m.kept);
     const size_t bounce_bytes = std::max((size_t)bounce_rows * pitch, (size_t)bounce_labels * sizeof(int));
-    void* bounce = nullptr;
-    if (bounce_bytes > 0) {
-        hipError_t e = hipMallocAsync(&bounce, bounce_bytes, st);
-        if (e != hipSuccess) return fail(MIPS_E_NOMEM, "mips_index_remove: hipMallocAsync(%zu) for the bounce buffer failed: %s", bounce_bytes, hipGetErrorString(e));
-    }
-    rc = remove_gather_rows(plan, keep, W, n, ix->rows, pitch, (uint8_t*)bounce, st);
-    if (rc == MIPS_OK && ix->plane > 0)
-        rc = remove_gather_rows(plan, keep, W, n, (uint8_t*)ix->rows_f32, (int64_t)ix->plane * sizeof(float), (uint8_t*)bounce, st);
-    if (rc == MIPS_OK && nlab > 0) rc = remove_gather_labels(lab_plan, keep, W, nlab, ix->labels, (int*)bounce, st);
-    if (bounce) {
-        hipError_t e = hipFreeAsync(bounce, st);
-        if (rc == MIPS_OK && e != hipSuccess) rc = fail(MIPS_E_HIP, "mips_index_remove: hipFreeAsync failed: %s", hipGetErrorString(e));
+    {
+        // the bounce buffer lives on the stream: released behind the gathers however this block is left
+        struct StreamAlloc {
+            void* p = nullptr;
+            hipStream_t st;
+            hipError_t freed = hipSuccess;
+            void release() {
+                if (p) freed = hipFreeAsync(p, st);
+                p = nullptr;
+            }
+            ~StreamAlloc() { release(); }
+        } bounce{nullptr, st};
+        if (bounce_bytes > 0) {
+            hipError_t e = hipMallocAsync(&bounce.p, bounce_bytes, st);
+            if (e != hipSuccess) return fail(MIPS_E_NOMEM, "mips_index_remove: hipMallocAsync(%zu) for the bounce buffer failed: %s", bounce_bytes, hipGetErrorString(e));
+        }
+        rc = remove_gather_rows(plan, keep, W, n, ix->rows, pitch, (uint8_t*)bounce.p, st);
+        if (rc == MIPS_OK && ix->plane > 0)
+            rc = remove_gather_rows(plan, keep, W, n, (uint8_t*)ix->rows_f32.p, (int64_t)ix->plane * sizeof(float), (uint8_t*)bounce.p, st);
+        if (rc == MIPS_OK && nlab > 0) rc = remove_gather_labels(lab_plan, keep, W, nlab, ix->labels, (int*)bounce.p, st);
+        bounce.release();
+        if (rc == MIPS_OK && bounce.freed != hipSuccess) rc = fail(MIPS_E_HIP, "mips_index_remove: hipFreeAsync failed: %s", hipGetErrorString(bounce.freed));
     }
     if (rc) return rc; // (rows may have moved already: the index is to be reset)
     ix->ntotal = plan.n_new;
     ix->nlabelled = nlab > 0 ? lab_plan.n_new : 0;
-    // the bf16 image of an fp32-exact index is derived data: rows from the first window that lost a row on are converted
-    // again by the next two-stage search (ensure_hi), the rows before it did not move
-    ix->hi_rows = std::min(ix->hi_rows, plan.first_row);
-    if (!ix->phi_override) ix->phi_valid = false;
-    ix->xmax2_valid = false;
-    ix->dres2_valid = false;
+    rows_changed(ix, plan.first_row); // (the rows before the first window that lost a row did not move)
     out_counts[0] = n - plan.n_new;
     out_counts[1] = ix->nlabelled;
     return MIPS_OK;

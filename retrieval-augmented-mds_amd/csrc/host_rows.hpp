@@ -46,7 +46,7 @@ int index_reconstruct(mips_index* ix, const int64_t* ids, int64_t n, int64_t idx
     rc = rows_ids_on_device(ix, ids, n, ids_dev, st, d_ids);
     if (rc) return rc;
     mips::RowsGatherArgs a;
-    a.rows = f32x ? (const void*)ix->rows_f32 : (const void*)ix->rows;
+    a.rows = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
     a.ld = f32x ? ix->plane : ix->ld;
     a.d = (int)ix->d;
     a.ntotal = ix->ntotal;
@@ -111,32 +111,30 @@ int index_score_subset(mips_index* ix, const void* q, int q_dtype, int64_t nq, c
         if (rc) return rc;
     }
     // the staged queries of the current scratch set may still be read by the tail of a split-tail search
-    if (ix->tail_pending[ix->cur_set]) {
-        HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[ix->cur_set], 0));
-        ix->tail_pending[ix->cur_set] = false;
-    }
+    rc = wait_for_tail(ix, st, /*both_sets=*/false);
+    if (rc) return rc;
     if (l2 && ix->ntotal > 0) {
         rc = compute_phi(ix, st);
         if (rc) return rc;
     }
     // the queries, staged as mips_search stages them (no padding rows: one thread reads one query row)
     const size_t row_bytes = (size_t)ix->ld * ix->qsize;
-    rc = ix->qbuf.ensure((size_t)nq * row_bytes);
+    rc = ix->cur.qbuf.ensure((size_t)nq * row_bytes);
     if (rc) return rc;
     if (f32x) {
-        rc = ix->qf32.ensure((size_t)nq * ix->plane * sizeof(float));
+        rc = ix->cur.qf32.ensure((size_t)nq * ix->plane * sizeof(float));
         if (rc) return rc;
-        rc = convert_into(ix, q, nq, q_dtype, q_dev, (uint8_t*)ix->qbuf.p, st, (float*)ix->qf32.p);
+        rc = convert_into(ix, q, nq, q_dtype, q_dev, (uint8_t*)ix->cur.qbuf.p, st, (float*)ix->cur.qf32.p);
     } else {
-        rc = convert_into(ix, q, nq, q_dtype, q_dev, (uint8_t*)ix->qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize);
+        rc = convert_into(ix, q, nq, q_dtype, q_dev, (uint8_t*)ix->cur.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize);
     }
     if (rc) return rc;
     const int64_t* d_ids;
     rc = rows_ids_on_device(ix, ids, npairs, ids_dev, st, d_ids);
     if (rc) return rc;
     mips::RowsScoreArgs a;
-    a.rows = f32x ? (const void*)ix->rows_f32 : (const void*)ix->rows;
-    a.y = f32x ? ix->qf32.p : ix->qbuf.p;
+    a.rows = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
+    a.y = f32x ? ix->cur.qf32.p : ix->cur.qbuf.p;
     a.ld = f32x ? ix->plane : ix->ld;
     a.ntotal = ix->ntotal;
     a.ids = d_ids;

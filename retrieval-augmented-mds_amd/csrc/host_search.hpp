@@ -36,9 +36,10 @@ int ensure_resolve_buffers(mips_index* ix, int64_t nq) {
 }
 
 // handoff: prepare the stream-ordered exact pass (resolve_flagged with skip_compact) -- the kernel's last workgroup writes
-// the flag list, clears the hit counters and copies the staged queries out when something was flagged (c.qbuf / c.qf32: where to)
+// the flag list, clears the hit counters and copies the staged queries out when something was flagged (c.qbuf / c.qf32: where to).
+// *nflag_dev: where the kernel counts the queries it flags (nullptr: the margin check is off)
 int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, int64_t nq, int k_fetch, int k_out, int normalize, const int64_t* ignore_dev,
-                float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool handoff) {
+                float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool handoff, unsigned** nflag_dev) {
     const bool f32x = ix->plane > 0;
     const int tld = f32x ? ix->hp : ix->ld; // row pitch of the scanned bf16 rows
     if (f32x) { // bf16 rows + residual bound up to date, max |x|^2 on the fp32 rows
@@ -46,7 +47,7 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
         if (rc0) return rc0;
     }
     if (!ix->tiny_words) {
-        HIP_TRY(hipMalloc((void**)&ix->tiny_words, 64));
+        HIP_TRY(hipMalloc((void**)&ix->tiny_words.p, 64));
         HIP_TRY(hipMemsetAsync(ix->tiny_words, 0, 64, st)); // the ticket starts at 0; the kernel's last workgroup resets it
     }
     const int ntiles = (int)((ix->ntotal + 15) / 16);
@@ -54,7 +55,7 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
     // the last one to sift; spreading thinner did not make the first tiles arrive sooner)
     const int nwg = (int)std::max<int64_t>(1, std::min<int64_t>(mips::TINY_MAX_WG, (ntiles + mips::TINY_WAVES - 1) / mips::TINY_WAVES));
     mips::TinyArgs a;
-    a.docs = f32x ? (const uint16_t*)ix->rows_hi : (const uint16_t*)ix->rows;
+    a.docs = (const uint16_t*)(f32x ? ix->rows_hi.p : ix->rows.p);
     a.rows_f32 = ix->rows_f32;
     a.plane = ix->plane;
     a.q = q_dev;
@@ -79,15 +80,15 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
     a.out_i = d_i;
     a.out_packed = packed ? d_i : nullptr;
     const size_t ncand = (size_t)nwg * mips::TINY_POOL; // per query: the 8 best of every workgroup
-    int rc = ix->part_s.ensure(16 * (ncand + nwg) * sizeof(float)); // + the workgroups' bounds behind the candidates
+    int rc = ix->cur.part_s.ensure(16 * (ncand + nwg) * sizeof(float)); // + the workgroups' bounds behind the candidates
     if (rc) return rc;
-    rc = ix->part_i.ensure(16 * ncand * sizeof(int));
+    rc = ix->cur.part_i.ensure(16 * ncand * sizeof(int));
     if (rc) return rc;
     mips::MergeArgs& m = a.m;
-    m.part_s = (const float*)ix->part_s.p;
-    m.part_i = (const int*)ix->part_i.p;
+    m.part_s = (const float*)ix->cur.part_s.p;
+    m.part_i = (const int*)ix->cur.part_i.p;
     m.ncand = (int)ncand;
-    m.pre_bnd = (const float*)ix->part_s.p + 16 * ncand;
+    m.pre_bnd = (const float*)ix->cur.part_s.p + 16 * ncand;
     m.npre = nwg;
     m.docs = a.docs;
     m.qbuf = nullptr;
@@ -108,34 +109,30 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
     m.xmax2 = ix->xmax2_dev;
     m.err_c = (double)ix->d * 1.1920928955078125e-07 * (f32x ? 1.01 : 1.0); // (F32: the scan's operands are bf16(q), bf16(x))
     m.dres2 = ix->dres2_dev;
-    ix->last_flagged = -1;
-    ix->last_rescanned = 0;
-    ix->last_unresolved = 0;
-    ix->last_nflag_dev = nullptr;
-    ix->first_nflag_dev = nullptr;
+    *nflag_dev = nullptr;
     if (c.margin != 0) {
-        rc = ix->mbnd.ensure(16 * sizeof(float));
+        rc = ix->cur.mbnd.ensure(16 * sizeof(float));
         if (rc) return rc;
-        rc = ix->mflag.ensure(16);
+        rc = ix->cur.mflag.ensure(16);
         if (rc) return rc;
         rc = ensure_xmax2(ix, st);
         if (rc) return rc;
         m.xmax2 = ix->xmax2_dev;
-        m.bnd = (float*)ix->mbnd.p;
-        m.flag = (unsigned char*)ix->mflag.p;
+        m.bnd = (float*)ix->cur.mbnd.p;
+        m.flag = (unsigned char*)ix->cur.mflag.p;
         m.nflag = ix->tiny_words + 1;
-        ix->last_nflag_dev = m.nflag;
+        *nflag_dev = m.nflag;
         if (handoff) {
             rc = ensure_resolve_buffers(ix, nq);
             if (rc) return rc;
-            if (f32x) rc = ix->qf32.ensure((size_t)16 * ix->plane * sizeof(float));
-            else rc = ix->qbuf.ensure((size_t)16 * ix->ld * 2);
+            if (f32x) rc = ix->cur.qf32.ensure((size_t)16 * ix->plane * sizeof(float));
+            else rc = ix->cur.qbuf.ensure((size_t)16 * ix->ld * 2);
             if (rc) return rc;
             a.res_ids = (int*)ix->ids.p;
             a.res_cnt = a.res_ids + nq;
             a.res_unres = (unsigned*)(a.res_ids + nq + 1);
             a.res_hit_n = (int*)ix->hit_n.p;
-            a.q_out = f32x ? ix->qf32.p : ix->qbuf.p;
+            a.q_out = f32x ? ix->cur.qf32.p : ix->cur.qbuf.p;
             if (f32x) c.qf32 = a.q_out; // (the exact pass reads the flagged queries from there)
             else c.qbuf = a.q_out;
             m.keyk = (float*)ix->keyk.p;
@@ -163,11 +160,12 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
 // rows per 8 flagged queries computing canonical scores, the hit lists ranked over the first results.
 // certify_now: the call synchronises anyway (host buffers / "margin_check" = 2): the count is read first, and a search that
 // flagged more than RESOLVE_MAX queries is handed to the tile re-scan (return value kUseRescan).  Otherwise everything is
-// enqueued blind; the counts travel to host-visible words for the next search to look at (mips_index::stats_host).
+// enqueued blind and the report names the two device words (the flagged count, what is still unresolved).
+// rep: the call's report -- on entry "unknown", with the first scan's counter in last_dev.
 constexpr int kUseRescan = 1;
 // skip_compact: the flag list, its count and the cleared counters are already on the device (the one-launch kernel's hand-off).
 // ignore / k_out: the fused hook call's ignore filter (ResolveArgs), d_s / d_i then are [nq][k_out].
-int resolve_flagged(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool certify_now,
+int resolve_flagged(mips_index* ix, const SearchCall& c, SearchReport& rep, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool certify_now,
                     bool skip_compact = false, const int64_t* ignore = nullptr, int k_out = 0) {
     if (k > mips::RESOLVE_OVF_K) return fail(MIPS_E_UNSUPPORTED, "resolve_flagged: k = %d exceeds RESOLVE_OVF_K", k);
     int rc = ensure_resolve_buffers(ix, nq); // (never reallocates behind a hand-off: same sizes as tiny_search asked for)
@@ -175,31 +173,29 @@ int resolve_flagged(mips_index* ix, const SearchCall& c, int64_t nq, int k, floa
     int* ids = (int*)ix->ids.p;
     int* cnt = ids + nq;
     unsigned* unres = (unsigned*)(ids + nq + 1);
-    if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host, 64, hipHostMallocDefault));
+    rc = ensure_nflag_host(ix);
+    if (rc) return rc;
     const int max_n = ix->resolve_budget > 0 ? std::min(ix->resolve_budget, mips::RESOLVE_MAX) : mips::RESOLVE_MAX;
     if (!skip_compact)
-        mips::compact_flags_kernel<<<1, 256, 0, st>>>((const unsigned char*)ix->mflag.p, (int)nq, ids, cnt, (int*)ix->hit_n.p, mips::RESOLVE_MAX, unres);
+        mips::compact_flags_kernel<<<1, 256, 0, st>>>((const unsigned char*)ix->cur.mflag.p, (int)nq, ids, cnt, (int*)ix->hit_n.p, mips::RESOLVE_MAX, unres);
     if (certify_now) {
         HIP_TRY(hipMemcpyAsync(&ix->nflag_host[0], cnt, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const int64_t n = (int64_t)ix->nflag_host[0];
-        ix->last_flagged = n;
-        ix->last_rescanned = 0;
-        ix->last_unresolved = 0;
+        rep.flagged = n;
         if (n == 0) return MIPS_OK;
         if (n > max_n && !skip_compact) return kUseRescan; // (the one-launch kernel's <= 16 queries have no tile re-scan to go to)
     }
     mips::ResolveArgs a;
     const bool f32x = ix->plane > 0;
-    a.rows = f32x ? (const void*)ix->rows_f32 : (const void*)ix->rows;
+    a.rows = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
     a.y = f32x ? c.qf32 : c.qbuf;
     a.ld = f32x ? ix->plane : ix->ld;
     a.ntotal = ix->ntotal;
     a.ids = ids;
     a.n_dev = cnt;
     a.max_n = max_n;
-    ix->last_max_n = a.max_n;
-    ix->last_fallback = false;
+    rep.max_n = max_n;
     a.keyk = (const float*)ix->keyk.p;
     a.qq = (const double*)ix->qqv.p;
     a.phi = ix->phi;
@@ -236,7 +232,7 @@ int resolve_flagged(mips_index* ix, const SearchCall& c, int64_t nq, int k, floa
         }
         rc = ensure_xmax2(ix, st);
         if (rc) return rc;
-        a.frows = f32x ? (const uint16_t*)ix->rows_hi : (const uint16_t*)ix->rows;
+        a.frows = (const uint16_t*)(f32x ? ix->rows_hi.p : ix->rows.p);
         a.fld = ffld;
         a.xmax2 = ix->xmax2_dev;
         a.dres2 = ix->dres2_dev;
@@ -267,16 +263,14 @@ int resolve_flagged(mips_index* ix, const SearchCall& c, int64_t nq, int k, floa
     else rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemBF16, true>) : go(mips::resolve_overflow_kernel<mips::ElemBF16, false>);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
-    ix->first_nflag_dev = (const int*)cnt;
-    ix->last_nflag_dev = unres;
+    rep.first_dev = cnt;
+    rep.last_dev = unres;
     if (certify_now) {
         HIP_TRY(hipMemcpyAsync(&ix->nflag_host[1], unres, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        ix->last_rescanned = ix->last_flagged > a.max_n ? 0 : ix->last_flagged; // (over the budget: nothing was settled)
-        ix->last_unresolved = (int64_t)ix->nflag_host[1];
-    } else {
-        ix->last_flagged = -1; // (device only: mips_index_margin_stats fetches the two counters when asked)
-    }
+        rep.rescanned = rep.settled();
+        rep.unresolved = (int64_t)ix->nflag_host[1];
+    } // (else device only: mips_index_margin_stats fetches the two counters when asked)
     return MIPS_OK;
 }
 
@@ -296,7 +290,8 @@ int widest_lists(const mips_index* ix, bool recheck) {
 //                        leave (ScanArgs::nq_dev), select, re-score and the scatter do the same
 // nsplit: few flagged queries = few query tiles, so each tile's scan is spread over more splits than the automatic choice makes
 // (0 = that choice; the caller's heuristic, which "nsplit" overrides)
-int rescan_flagged(mips_index* ix, const SearchCall& c, int wide, const int* ids, int64_t n, const int* cnt, int nsplit, int k, float* d_s,
+// rep.last_dev becomes the re-scan's own counter: the queries still flagged on the widest lists
+int rescan_flagged(mips_index* ix, const SearchCall& c, SearchReport& rep, int wide, const int* ids, int64_t n, const int* cnt, int nsplit, int k, float* d_s,
                    int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st) {
     const int64_t n_pad = query_pad(ix, n);
     const size_t row_bytes = (size_t)c.ld * ix->qsize;
@@ -319,7 +314,7 @@ int rescan_flagged(mips_index* ix, const SearchCall& c, int wide, const int* ids
                                                                                             (unsigned char*)ix->qf32b.p, cnt);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemsetAsync(ix->gthr.p, 0, (size_t)(n_pad * 8 + 4) * sizeof(unsigned), st)); // insert bounds, error word, flag counter
+    HIP_TRY(hipMemsetAsync(ix->cur.gthr.p, 0, (size_t)(n_pad * 8 + 4) * sizeof(unsigned), st)); // insert bounds, error word, flag counter
     r.optimistic = false;
     r.rescan = true;
     r.nq_dev = cnt;
@@ -327,8 +322,8 @@ int rescan_flagged(mips_index* ix, const SearchCall& c, int wide, const int* ids
     r.timed = false; // the bench's event window times the first scan only, and last_kernel keeps naming it
     float* ts = (float*)ix->tmp_s.p;
     int64_t* ti = (int64_t*)ix->tmp_i.p;
-    if (wide == 32) rc = launch_search<32>(ix, r, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st);
-    else rc = launch_search<16>(ix, r, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st);
+    if (wide == 32) rc = launch_search<32>(ix, r, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st, &rep.last_dev);
+    else rc = launch_search<16>(ix, r, n, k, ts, ti, packed ? ti : nullptr, idx_offset, st, &rep.last_dev);
     if (rc) return rc;
     if (packed) {
         mips::scatter_i64_kernel<<<grid_for(n * 2 * k, 256), 256, 0, st>>>(ti, ids, n, 2 * k, d_i, cnt);
@@ -348,33 +343,27 @@ int rescan_flagged(mips_index* ix, const SearchCall& c, int wide, const int* ids
 // short sub-lists must not stand uncertified -- so this re-scan runs exactly then (its launches are sized by a count that is 0
 // otherwise) and its own still-flagged count replaces the exact pass's "unresolved".
 template <int KL>
-int rescan_on_stream(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st,
+int rescan_on_stream(mips_index* ix, const SearchCall& c, SearchReport& rep, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st,
                      bool recheck, int gate_above = -1) {
     const int wide = widest_lists<KL>(ix, recheck);
-    if (gate_above < 0) {
-        ix->last_flagged = -1; // (device only)
-        ix->last_max_n = 0;
-    }
-    if (wide == 0) return MIPS_OK; // already on the widest lists: counted only
+    if (wide == 0) return MIPS_OK; // already on the widest lists: counted only (rep.last_dev: the first scan's counter)
     int rc = ix->ids.ensure((size_t)(nq + 4) * sizeof(int));
     if (rc) return rc;
     int* ids = (int*)ix->ids.p;
     int* cnt = ids + nq + (gate_above >= 0 ? 2 : 0); // (gated: the exact pass's own count and unresolved counter stay where they are)
     unsigned* const exact_unres = (unsigned*)(ids + nq + 1);
-    const int* const first_keep = ix->first_nflag_dev;
-    mips::compact_flags_kernel<<<1, 256, 0, st>>>((const unsigned char*)ix->mflag.p, (int)nq, ids, cnt, nullptr, 0, nullptr, gate_above);
+    mips::compact_flags_kernel<<<1, 256, 0, st>>>((const unsigned char*)ix->cur.mflag.p, (int)nq, ids, cnt, nullptr, 0, nullptr, gate_above);
     // the flagged queries are few: spread each of their tiles over many CUs
-    rc = rescan_flagged(ix, c, wide, ids, nq, cnt, nq <= 4096 ? 128 : nq <= 8192 ? 64 : 0, k, d_s, d_i, packed, idx_offset, st);
+    rc = rescan_flagged(ix, c, rep, wide, ids, nq, cnt, nq <= 4096 ? 128 : nq <= 8192 ? 64 : 0, k, d_s, d_i, packed, idx_offset, st);
     if (rc) return rc;
     if (gate_above >= 0) { // statistics stay the exact pass's; if this re-scan ran, what IT still flags is what is unresolved
-        mips::adopt_rescan_count_kernel<<<1, 1, 0, st>>>(cnt, ix->last_nflag_dev, exact_unres);
+        mips::adopt_rescan_count_kernel<<<1, 1, 0, st>>>(cnt, rep.last_dev, exact_unres);
         HIP_TRY(hipGetLastError());
-        ix->first_nflag_dev = first_keep;
-        ix->last_nflag_dev = exact_unres;
-        ix->last_fallback = true;
+        rep.last_dev = exact_unres; // (first_dev, max_n: as the exact pass left them)
+        rep.fallback = true;
         return MIPS_OK;
     }
-    ix->first_nflag_dev = (const int*)cnt; // last_nflag_dev: the re-scan's own counter (still flagged on the widest lists)
+    rep.first_dev = cnt; // (last_dev: the re-scan's own counter)
     return MIPS_OK;
 }
 
@@ -385,57 +374,53 @@ int rescan_on_stream(mips_index* ix, const SearchCall& c, int64_t nq, int k, flo
 // when the call may synchronise (host buffers, "margin_check" = 2), here: the flag list is read back and rescan_flagged runs in
 // its synchronising form.  Queries still flagged after that are counted as unresolved (mips_index_margin_stats).
 template <int KL>
-int finish_margin(mips_index* ix, const SearchCall& c, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool out_dev,
+int finish_margin(mips_index* ix, const SearchCall& c, SearchReport& rep, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool out_dev,
                   hipStream_t st, bool recheck) {
-    ix->last_flagged = -1;
-    ix->last_rescanned = 0;
-    ix->last_unresolved = 0;
-    ix->first_nflag_dev = nullptr;
     if (!call_certifies(c.margin, out_dev)) return MIPS_OK; // off, or counted on the device only
     const bool stream_ordered = out_dev && c.margin == 3;
     if (ix->opt_resolve != 0 && (c.plane > 0 ? c.plane : c.ld) <= 1024) {
-        const int r = resolve_flagged(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, !stream_ordered);
+        const int r = resolve_flagged(ix, c, rep, nq, k, d_s, d_i, packed, idx_offset, st, !stream_ordered);
         if (r == MIPS_OK && stream_ordered && recheck) {
             const int max_n = ix->resolve_budget > 0 ? std::min(ix->resolve_budget, mips::RESOLVE_MAX) : mips::RESOLVE_MAX;
-            if (nq > max_n) return rescan_on_stream<KL>(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, recheck, max_n);
+            if (nq > max_n) return rescan_on_stream<KL>(ix, c, rep, nq, k, d_s, d_i, packed, idx_offset, st, recheck, max_n);
         }
-        if (r != kUseRescan) return r;
-        ix->first_nflag_dev = nullptr; // (more flagged than the exact pass takes: the tile re-scan below, which synchronises)
+        if (r != kUseRescan) return r; // (else more flagged than the exact pass takes: the tile re-scan below, which synchronises)
     } else if (stream_ordered) {
-        return rescan_on_stream<KL>(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, recheck);
+        return rescan_on_stream<KL>(ix, c, rep, nq, k, d_s, d_i, packed, idx_offset, st, recheck);
     }
-    if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host, 64, hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->last_nflag_dev, 4, hipMemcpyDeviceToHost, st));
+    int rc = ensure_nflag_host(ix);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->nflag_host, rep.last_dev, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t n = (int64_t)ix->nflag_host[0];
-    ix->last_flagged = n;
+    rep.flagged = n;
     if (n == 0) return MIPS_OK;
     const int wide = widest_lists<KL>(ix, recheck);
     if (wide == 0) { // already on the widest lists this storage type has
-        ix->last_unresolved = n;
+        rep.unresolved = n;
         return MIPS_OK;
     }
     // flagged query numbers
     std::string flags((size_t)nq, '\0');
-    HIP_TRY(hipMemcpyAsync(&flags[0], ix->mflag.p, (size_t)nq, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&flags[0], ix->cur.mflag.p, (size_t)nq, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     std::vector<int> ids_h;
     for (int64_t q = 0; q < nq && (int64_t)ids_h.size() < n; ++q)
         if (flags[(size_t)q]) ids_h.push_back((int)q);
     if ((int64_t)ids_h.size() != n)
         return fail(MIPS_E_HIP, "margin check: flag count %lld does not match the flag array (%lld)", (long long)n, (long long)ids_h.size());
-    int rc = ix->ids.ensure((size_t)n * sizeof(int));
+    rc = ix->ids.ensure((size_t)n * sizeof(int));
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(ix->ids.p, ids_h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
     // (the automatic split choice stops at 64; one 128-query tile of the three-segment scan on 64 workgroups took 17 ms at
     // 2^20 x 768)
     const int nsplit = n <= 1024 ? (int)std::max<int64_t>(64, std::min<int64_t>(256, round_up(512 / ((n + 127) / 128), 8))) : 0;
-    rc = rescan_flagged(ix, c, wide, (const int*)ix->ids.p, n, nullptr, nsplit, k, d_s, d_i, packed, idx_offset, st);
+    rc = rescan_flagged(ix, c, rep, wide, (const int*)ix->ids.p, n, nullptr, nsplit, k, d_s, d_i, packed, idx_offset, st);
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->last_nflag_dev, 4, hipMemcpyDeviceToHost, st)); // still flagged on the widest lists
+    HIP_TRY(hipMemcpyAsync(ix->nflag_host, rep.last_dev, 4, hipMemcpyDeviceToHost, st)); // still flagged on the widest lists
     HIP_TRY(hipStreamSynchronize(st));
-    ix->last_rescanned = n;
-    ix->last_unresolved = (int64_t)ix->nflag_host[0];
+    rep.rescanned = n;
+    rep.unresolved = (int64_t)ix->nflag_host[0];
     return MIPS_OK;
 }
 
@@ -444,7 +429,7 @@ int finish_margin(mips_index* ix, const SearchCall& c, int64_t nq, int k, float*
 // queries qhi; the re-score and the margin check still run on the fp32 rows (SearchCall::stage1).  Queries the widened margin
 // cannot certify are settled by finish_margin, which sees the call as it came in.
 template <int KL>
-int scan_and_finish(mips_index* ix, const SearchCall& c, const PoolPolicy& pol, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed,
+int scan_and_finish(mips_index* ix, const SearchCall& c, SearchReport& rep, const PoolPolicy& pol, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed,
                     int64_t idx_offset, bool out_dev, hipStream_t st, hipStream_t tail_st, bool split) {
     SearchCall first = c;
     first.optimistic = pol.optimistic;
@@ -456,23 +441,21 @@ int scan_and_finish(mips_index* ix, const SearchCall& c, const PoolPolicy& pol, 
         first.rescore_ld = c.plane;
         first.qbuf = ix->qhi.p;
     }
-    int rc = launch_search<KL>(ix, first, nq, k, d_s, d_i, packed ? d_i : nullptr, idx_offset, st, tail_st, split);
+    int rc = launch_search<KL>(ix, first, nq, k, d_s, d_i, packed ? d_i : nullptr, idx_offset, st, &rep.last_dev, tail_st, split);
     if (rc) return rc;
     if (split) { // scan on st, tail on tail_st: the certificate, when asked for, is part of the tail
-        ix->last_flagged = -1;
-        ix->first_nflag_dev = nullptr;
         if (c.margin == 3 && out_dev && ix->opt_resolve != 0 && (c.plane > 0 ? c.plane : c.ld) <= 1024) {
-            rc = resolve_flagged(ix, c, nq, k, d_s, d_i, packed, idx_offset, tail_st, false);
+            rc = resolve_flagged(ix, c, rep, nq, k, d_s, d_i, packed, idx_offset, tail_st, false);
             if (rc) return rc;
-            HIP_TRY(hipEventRecord(ix->tail_done[ix->cur_set], tail_st)); // (supersedes the record behind the re-score: the exact
-            ix->tail_pending[ix->cur_set] = true;                         // pass reads this set's staged queries)
+            HIP_TRY(hipEventRecord(ix->cur.tail_done, tail_st)); // (supersedes the record behind the re-score: the exact
+            ix->cur.tail_pending = true;                         // pass reads this set's staged queries)
         }
         return MIPS_OK;
     }
-    rc = finish_margin<KL>(ix, c, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, pol.recheck);
+    rc = finish_margin<KL>(ix, c, rep, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, pol.recheck);
     // the optimistic scan pays while few queries need the second one: after a synchronising call that sent more than an eighth
     // (and at least 64) there, pool_policy skips it for the next 8 calls
-    if (!rc && pol.recheck && ix->opt_f32_fast != 2 && ix->last_flagged >= 64 && ix->last_flagged * 8 > nq) ix->fast_skip = 8;
+    if (!rc && pol.recheck && ix->opt_f32_fast != 2 && rep.flagged >= 64 && rep.flagged * 8 > nq) ix->fast_skip = 8;
     return rc;
 }
 

@@ -1,7 +1,8 @@
 // Host side of libmips_hip.so, part 1 of 3 (included by mips_hip.hip, one translation unit): error reporting, device / stream
-// helpers, the index object (what PERSISTS between calls: storage in HBM, scratch, the caller's options, statistics), the value
-// that describes ONE call in progress (SearchCall: passed by reference, never stored on the index) and what keeps the index
-// consistent (growth, phi, row norms, the bf16 image of an fp32-exact index, stream ordering).
+// helpers, the types that own a device resource, the index object (what PERSISTS between calls: storage in HBM, scratch, the
+// caller's options, the report of the last search), the value that describes ONE call in progress (SearchCall: passed by
+// reference, never stored on the index) and what keeps the index consistent (growth, rows_changed, phi, row norms, the bf16
+// image of an fp32-exact index, stream ordering, the two scratch sets).
 #pragma once
 
 namespace {
@@ -43,9 +44,46 @@ inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 constexpr int64_t kRowAlign = 256;   // index capacity granule: the largest document tile of any scan variant
 constexpr int64_t kQueryAlign = 256; // query staging buffer granule: the largest power-of-two query tile of any scan variant
 
+// ---- What owns a device resource of the index.  Each frees what it holds when it goes (errors of the frees are ignored),
+// cannot be copied and can be moved, so std::swap exchanges two of them; `delete ix` is the whole of mips_index_destroy.
+// A handle released by Free: the exact-size device arrays (sizes are the caller's: never through Buffer::ensure), the pinned host
+// words and the events.  Converts to the handle it holds.
+template <class H, auto Free>
+struct Owned {
+    H p = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : p(o.p) { o.p = nullptr; }
+    Owned& operator=(Owned&& o) noexcept { // (what this held leaves with o)
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~Owned() {
+        if (p) (void)Free(p);
+    }
+    operator H() const { return p; }
+};
+template <class T>
+using DeviceArray = Owned<T*, hipFree>;
+using PinnedWords = Owned<unsigned*, hipHostFree>; // 64 bytes of pinned host memory
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+inline hipError_t create_event(Event& e, bool timing) {
+    return timing ? hipEventCreate(&e.p) : hipEventCreateWithFlags(&e.p, hipEventDisableTiming);
+}
+
+// Growable device scratch: grows by a quarter over what is asked for, never shrinks
 struct Buffer {
     void* p = nullptr;
     size_t bytes = 0;
+    Buffer() = default;
+    Buffer(Buffer&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+    Buffer& operator=(Buffer&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~Buffer() {
+        if (p) (void)hipFree(p);
+    }
     int ensure(size_t need) {
         if (need <= bytes) return MIPS_OK;
         if (p) (void)hipFree(p);
@@ -60,11 +98,15 @@ struct Buffer {
         bytes = want;
         return MIPS_OK;
     }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
+};
+
+// The scratch a search's scan and tail share.  Split-tail searches (mips_search_split) run the scan on one stream and select +
+// exact re-score on another, so the NEXT search's scan can start behind this one's: two sets alternate, and each carries the
+// event its tail records and whether a tail may still be reading it.
+struct ScratchSet {
+    Buffer qbuf, qf32, gthr, part_s, part_i, cand, mbnd, mflag;
+    Event tail_done;
+    bool tail_pending = false;
 };
 
 int grid_for(int64_t items, int block) {
@@ -85,29 +127,29 @@ struct mips_index {
     int metric = MIPS_METRIC_IP;
     int64_t ntotal = 0;
     int64_t capacity = 0; // rows allocated, multiple of TM
-    uint8_t* rows = nullptr; // [capacity][ld] elements of esize bytes
+    DeviceArray<uint8_t> rows; // [capacity][ld] elements of esize bytes
     // fp32-exact mode (doc_dtype F32): rows = bf16 planes [hi | lo] (ld = 2 * plane) for the scan,
     // rows_f32 = the fp32 originals [capacity][plane] for the exact re-score; qf32 = staged fp32 queries
     int plane = 0;
-    float* rows_f32 = nullptr;
+    DeviceArray<float> rows_f32;
     // two-stage search of the fp32-exact index ("f32_fast", d <= 1024): rows_hi = bf16(x) alone at a row pitch the
     // query-stationary kernels take ([capacity][hp]; converted lazily from rows_f32 up to hi_rows).  Stage 1 scans it
     // like a bf16 index and re-scores on the fp32 rows; the margin check, widened by the representation error
     // |x - bf16 x| |q| + |bf16 x| |q - bf16 q|, sends the queries it cannot certify to the three-segment scan.
-    uint8_t* rows_hi = nullptr;
+    DeviceArray<uint8_t> rows_hi;
     int hp = 0;
     int64_t hi_rows = 0;
-    double* dres2_dev = nullptr; // max_i |x_i - bf16 x_i|^2
+    DeviceArray<double> dres2_dev; // max_i |x_i - bf16 x_i|^2
     bool dres2_valid = false;
     int opt_f32_fast = 1;        // 0 off, 1 when the call may synchronise (host buffers / margin_check = 2), 2 always
-    const int* first_nflag_dev = nullptr; // flagged count of the first scan of the last mode-3 search (margin stats)
     int fast_skip = 0;           // calls left to skip stage 1 for: set by a SYNCHRONISING call that flagged too many queries for the
                                  // optimistic scan to pay (its count is known when it returns; stream-ordered calls never set it,
                                  // so what a search does depends on the calls before it, not on when a device store lands)
     bool phi_valid = false;
     bool phi_override = false; // phi was set from outside (global maximum of a sharded index): adds do not reset it
     double phi = 0.0;
-    Buffer qbuf, qf32, part_s, part_i, stage, out_s, out_i, scalar, gthr, cand;
+    ScratchSet cur, alt; // the scratch set in use and the other one (swap_scratch_sets)
+    Buffer stage, out_s, out_i, scalar;
     // ring of HIP event pairs around the scan kernel (bench.py reads the average launch duration)
     static constexpr int kEvRing = 128;
     // tuning knobs (mips_index_set_param); 0 = automatic
@@ -116,14 +158,14 @@ struct mips_index {
     int opt_spin_limit = 0; // test-only: polls of the split barrier before a wave gives up (0 = 1 << 22, < 0 = flag forced)
     // sticky scan-error flag: one pinned, mapped host word.  The exact re-score sets it (system-scope store) when
     // the scan kernel of its call gave up on the split barrier; the host reads it without a device round trip.
-    unsigned* sticky_host = nullptr;
-    unsigned* sticky_dev = nullptr;
+    PinnedWords sticky_host;
+    unsigned* sticky_dev = nullptr; // (the same words as the device sees them)
     char last_kernel[96] = ""; // instance mips_search dispatched last (mips_index_last_kernel)
     // margin check.  0 = off, 1 = flag and count on the device (never synchronises), 2 = certify:
     // synchronise, re-scan the flagged queries with the widest lists.  Host-output searches always certify (they
     // synchronise anyway) unless the check is off.  This is the caller's knob: a call acts on margin_mode() of it.
     int opt_margin = 1;
-    Buffer mbnd, mflag, qbuf2, qf32b, tmp_s, tmp_i, ids, qhi, qerr2, keyk, qqv, hit_d, hit_i, hit_n, qnorm;
+    Buffer qbuf2, qf32b, tmp_s, tmp_i, ids, qhi, qerr2, keyk, qqv, hit_d, hit_i, hit_n, qnorm;
     // wide top-k (mips_search_wide, host_wide.hpp): candidate segments (fixed budget), pools [queries][k'], segment counters,
     // per-query thresholds / seeds / flags
     Buffer w_seg, w_pool, w_cnt, w_misc;
@@ -141,38 +183,29 @@ struct mips_index {
     // grouped searches (mips_search_wide_grp / mips_range_search_grp): one int32 label per row in storage of its own, allocated in
     // whole 128-row tiles for at least `capacity` rows (mips_index_set_labels grows it and keeps what it held, so it survives the
     // growth of the rows); rows [0, nlabelled) carry a label.  grp_q: the staged per-query labels of the call in flight.
-    int* labels = nullptr;
+    DeviceArray<int> labels;
     int64_t labels_cap = 0, nlabelled = 0;
     Buffer grp_q;
     int opt_resolve = 1; // flagged queries: 1 = exact brute-force resolution (resolve_kernels.hpp; 2 = its plain form, no MFMA pre-filter), 0 = re-scan with the widest lists
     int resolve_budget = 0; // "resolve_budget" > 0: flagged queries a search resolves at most (0 = RESOLVE_MAX); a search that flags
                             // more keeps its first results (counted unresolved) -- or, if its first scan was an optimistic one,
                             // goes through the stream-ordered re-scan with true K' = 32 lists
-    double* xmax2_dev = nullptr; // max_i |x_i|^2 of the LOCAL rows, on the device (no host copy: never synchronises)
+    DeviceArray<double> xmax2_dev; // max_i |x_i|^2 of the LOCAL rows, on the device (no host copy: never synchronises)
     bool xmax2_valid = false;
-    unsigned* nflag_host = nullptr; // pinned: flagged-query count of the last certified search
-    int64_t last_flagged = -1, last_rescanned = 0, last_unresolved = 0;
-    bool last_fallback = false; // the last search enqueued the gated fall-back re-scan behind its exact pass
-    int last_max_n = 0; // flagged queries the exact pass of the last search would resolve at most (statistics: over budget = none settled)
-    unsigned* last_nflag_dev = nullptr;
-    // Split-tail searches (mips_search_split): the scan runs on one stream, select + exact re-score on another, so the
-    // NEXT search's scan can start behind this one's.  Two scratch sets alternate; `alt_*` is the one not in use.
-    Buffer alt_qbuf, alt_qf32, alt_gthr, alt_part_s, alt_part_i, alt_cand, alt_mbnd, alt_mflag;
-    int cur_set = 0;
-    hipEvent_t scan_done = nullptr;
-    hipEvent_t tail_done[2] = {nullptr, nullptr};
-    bool tail_pending[2] = {false, false};
+    PinnedWords nflag_host; // flagged-query counts a certifying search reads back (allocated on first use: ensure_nflag_host)
+    SearchReport report;    // what the last search call flagged and settled (search_report.hpp; mips_index_margin_stats)
+    Event scan_done;        // split-tail searches: the tail stream waits for the scan (ScratchSet)
     int opt_tiny = 1;              // 1 = searches of <= 16 queries over a small bf16 index take the one-launch kernel
-    unsigned* tiny_words = nullptr; // [0] ticket (reset by the kernel's last workgroup), [1] flag counter
+    DeviceArray<unsigned> tiny_words; // [0] ticket (reset by the kernel's last workgroup), [1] flag counter
     int opt_variant = 0; // 0 = automatic, 1 = scan_kernel (128x128 tiles), 3 = scan_kernel_v3 (32x32x16), 4 = scan_kernel_v4 (16x16x32)
-    hipEvent_t ev0[kEvRing] = {}, ev1[kEvRing] = {};
+    Event ev0[kEvRing], ev1[kEvRing];
     int ev_count = 0; // pairs recorded since the last reset (saturates at kEvRing)
     bool timing_armed = false; // event pairs are recorded only inside a measurement window (mips_scan_timing reset):
                                // an event record costs ~5.7 us of stream time on this part, 11 us per search
     int ev_next = 0;
     // The scratch buffers are shared by every call on this index.  Calls on ONE stream are ordered by the
     // stream; a call arriving on another stream first waits for `busy`, recorded at the end of the last call.
-    hipEvent_t busy = nullptr;
+    Event busy;
     hipStream_t last_stream = nullptr;
     bool has_last = false;
 };
@@ -249,8 +282,8 @@ struct StreamOrder {
 // first (the next call on the index, mips_index_check_error, a host-output search) reports and clears it.
 int take_scan_error(mips_index* ix, const char* who) {
     if (ix->sticky_host == nullptr) return MIPS_OK;
-    if (__atomic_load_n(ix->sticky_host, __ATOMIC_ACQUIRE) == 0u) return MIPS_OK;
-    __atomic_store_n(ix->sticky_host, 0u, __ATOMIC_RELEASE);
+    if (__atomic_load_n(ix->sticky_host.p, __ATOMIC_ACQUIRE) == 0u) return MIPS_OK;
+    __atomic_store_n(ix->sticky_host.p, 0u, __ATOMIC_RELEASE);
     return fail(MIPS_E_SCAN_TIMEOUT,
                 "%s: a scan kernel on this index gave up on its block barrier (spin bound reached); the results of "
                 "that search were poisoned (idx %d, NaN scores) and must be discarded", who, MIPS_IDX_POISON);
@@ -268,29 +301,21 @@ int grow(mips_index* ix, int64_t need_rows, hipStream_t st, bool exact = false) 
     if (need_rows <= ix->capacity) return MIPS_OK;
     int64_t cap = exact ? need_rows : std::max<int64_t>(need_rows, ix->capacity + ix->capacity / 2);
     cap = round_up(cap, kRowAlign);
-    uint8_t* fresh = nullptr;
-    float* fresh32 = nullptr;
-    uint8_t* fresh_hi = nullptr;
+    DeviceArray<uint8_t> fresh, fresh_hi; // (swapped into the index at the end: the old storage goes with them, behind the
+    DeviceArray<float> fresh32;           // synchronisation below; on an error return what was allocated goes)
     const size_t row_bytes = (size_t)ix->ld * ix->esize;
     const size_t bytes = (size_t)cap * row_bytes;
     const size_t b32 = (size_t)cap * ix->plane * sizeof(float);
-    hipError_t e = hipMalloc((void**)&fresh, bytes);
+    hipError_t e = hipMalloc((void**)&fresh.p, bytes);
     if (e != hipSuccess) return fail(MIPS_E_NOMEM, "hipMalloc(%zu) for the index failed: %s", bytes, hipGetErrorString(e));
     if (ix->plane > 0) {
-        e = hipMalloc((void**)&fresh32, b32);
-        if (e != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(MIPS_E_NOMEM, "hipMalloc(%zu) for the fp32 rows failed: %s", b32, hipGetErrorString(e));
-        }
+        e = hipMalloc((void**)&fresh32.p, b32);
+        if (e != hipSuccess) return fail(MIPS_E_NOMEM, "hipMalloc(%zu) for the fp32 rows failed: %s", b32, hipGetErrorString(e));
     }
     const size_t bhi = (size_t)cap * ix->hp * 2;
     if (ix->plane > 0 && ix->hp > 0) {
-        e = hipMalloc((void**)&fresh_hi, bhi);
-        if (e != hipSuccess) {
-            (void)hipFree(fresh);
-            (void)hipFree(fresh32);
-            return fail(MIPS_E_NOMEM, "hipMalloc(%zu) for the bf16 rows of the fp32 index failed: %s", bhi, hipGetErrorString(e));
-        }
+        e = hipMalloc((void**)&fresh_hi.p, bhi);
+        if (e != hipSuccess) return fail(MIPS_E_NOMEM, "hipMalloc(%zu) for the bf16 rows of the fp32 index failed: %s", bhi, hipGetErrorString(e));
     }
     // copy the rows in use; rows past ntotal are read by the last (ragged) tile: keep them defined
     const size_t used = (size_t)ix->ntotal * row_bytes;
@@ -298,23 +323,15 @@ int grow(mips_index* ix, int64_t need_rows, hipStream_t st, bool exact = false) 
     if (used) e = hipMemcpyAsync(fresh, ix->rows, used, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipMemsetAsync(fresh + used, 0, bytes - used, st);
     if (e == hipSuccess && fresh32 && u32) e = hipMemcpyAsync(fresh32, ix->rows_f32, u32, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess && fresh32) e = hipMemsetAsync((char*)fresh32 + u32, 0, b32 - u32, st);
+    if (e == hipSuccess && fresh32) e = hipMemsetAsync((char*)fresh32.p + u32, 0, b32 - u32, st);
     const size_t uhi = (size_t)ix->hi_rows * ix->hp * 2;
     if (e == hipSuccess && fresh_hi && uhi) e = hipMemcpyAsync(fresh_hi, ix->rows_hi, uhi, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && fresh_hi) e = hipMemsetAsync(fresh_hi + uhi, 0, bhi - uhi, st);
-    if (e == hipSuccess && ix->rows) e = hipStreamSynchronize(st); // the old storage is freed below
-    if (e != hipSuccess) {
-        (void)hipFree(fresh);
-        if (fresh32) (void)hipFree(fresh32);
-        if (fresh_hi) (void)hipFree(fresh_hi);
-        return fail(MIPS_E_HIP, "growing the index to %lld rows failed: %s", (long long)cap, hipGetErrorString(e));
-    }
-    if (ix->rows) (void)hipFree(ix->rows);
-    if (ix->rows_f32) (void)hipFree(ix->rows_f32);
-    if (ix->rows_hi) (void)hipFree(ix->rows_hi);
-    ix->rows = fresh;
-    ix->rows_f32 = fresh32;
-    ix->rows_hi = fresh_hi;
+    if (e == hipSuccess && ix->rows) e = hipStreamSynchronize(st); // the old storage is freed when this returns
+    if (e != hipSuccess) return fail(MIPS_E_HIP, "growing the index to %lld rows failed: %s", (long long)cap, hipGetErrorString(e));
+    std::swap(ix->rows, fresh);
+    std::swap(ix->rows_f32, fresh32);
+    std::swap(ix->rows_hi, fresh_hi);
     ix->capacity = cap;
     return MIPS_OK;
 }
@@ -393,7 +410,7 @@ int compute_phi(mips_index* ix, hipStream_t st) {
             mips::row_sumsq_max_kernel<mips::ElemF32><<<grid, 256, 0, st>>>(ix->rows_f32, ix->ntotal, ix->plane,
                                                                              (unsigned long long*)ix->scalar.p);
         else if (ix->esize == 2)
-            mips::row_sumsq_max_kernel<mips::ElemBF16><<<grid, 256, 0, st>>>((const uint16_t*)ix->rows, ix->ntotal, ix->ld,
+            mips::row_sumsq_max_kernel<mips::ElemBF16><<<grid, 256, 0, st>>>((const uint16_t*)ix->rows.p, ix->ntotal, ix->ld,
                                                                               (unsigned long long*)ix->scalar.p);
         else
             mips::row_sumsq_max_kernel<mips::ElemF8><<<grid, 256, 0, st>>>(ix->rows, ix->ntotal, ix->ld,
@@ -411,13 +428,13 @@ int compute_phi(mips_index* ix, hipStream_t st) {
 // max_i |x_i|^2 of the local rows into a device scalar, stream-ordered, no host copy (the margin check's error bound)
 int ensure_xmax2(mips_index* ix, hipStream_t st) {
     if (ix->xmax2_valid) return MIPS_OK;
-    if (!ix->xmax2_dev) HIP_TRY(hipMalloc((void**)&ix->xmax2_dev, 8));
+    if (!ix->xmax2_dev) HIP_TRY(hipMalloc((void**)&ix->xmax2_dev.p, 8));
     HIP_TRY(hipMemsetAsync(ix->xmax2_dev, 0, 8, st));
     if (ix->ntotal > 0) {
         const int grid = (int)((ix->ntotal + 255) / 256);
-        unsigned long long* out = (unsigned long long*)ix->xmax2_dev;
+        unsigned long long* out = (unsigned long long*)ix->xmax2_dev.p;
         if (ix->plane > 0) mips::row_sumsq_max_kernel<mips::ElemF32><<<grid, 256, 0, st>>>(ix->rows_f32, ix->ntotal, ix->plane, out);
-        else if (ix->esize == 2) mips::row_sumsq_max_kernel<mips::ElemBF16><<<grid, 256, 0, st>>>((const uint16_t*)ix->rows, ix->ntotal, ix->ld, out);
+        else if (ix->esize == 2) mips::row_sumsq_max_kernel<mips::ElemBF16><<<grid, 256, 0, st>>>((const uint16_t*)ix->rows.p, ix->ntotal, ix->ld, out);
         else mips::row_sumsq_max_kernel<mips::ElemF8><<<grid, 256, 0, st>>>(ix->rows, ix->ntotal, ix->ld, out);
         HIP_TRY(hipGetLastError());
     }
@@ -431,16 +448,16 @@ int ensure_hi(mips_index* ix, hipStream_t st) {
         const int64_t nr = ix->ntotal - ix->hi_rows;
         const int64_t items = nr * (ix->hp / 8);
         mips::convert_rows_kernel<float><<<grid_for(items, 256), 256, 0, st>>>(ix->rows_f32 + (size_t)ix->hi_rows * ix->plane, nr, ix->plane,
-                                                                               (uint16_t*)ix->rows_hi + (size_t)ix->hi_rows * ix->hp, ix->hp);
+                                                                               (uint16_t*)ix->rows_hi.p + (size_t)ix->hi_rows * ix->hp, ix->hp);
         HIP_TRY(hipGetLastError());
         ix->hi_rows = ix->ntotal;
     }
     if (!ix->dres2_valid) {
-        if (!ix->dres2_dev) HIP_TRY(hipMalloc((void**)&ix->dres2_dev, 8));
+        if (!ix->dres2_dev) HIP_TRY(hipMalloc((void**)&ix->dres2_dev.p, 8));
         HIP_TRY(hipMemsetAsync(ix->dres2_dev, 0, 8, st));
         if (ix->ntotal > 0) {
             mips::row_resid_sumsq_max_kernel<<<(int)((ix->ntotal + 255) / 256), 256, 0, st>>>(ix->rows_f32, ix->ntotal, ix->plane,
-                                                                                             (unsigned long long*)ix->dres2_dev);
+                                                                                             (unsigned long long*)ix->dres2_dev.p);
             HIP_TRY(hipGetLastError());
         }
         ix->dres2_valid = true;
@@ -448,16 +465,34 @@ int ensure_hi(mips_index* ix, hipStream_t st) {
     return MIPS_OK;
 }
 
-void swap_scratch_sets(mips_index* ix) {
-    std::swap(ix->qbuf, ix->alt_qbuf);
-    std::swap(ix->qf32, ix->alt_qf32);
-    std::swap(ix->gthr, ix->alt_gthr);
-    std::swap(ix->part_s, ix->alt_part_s);
-    std::swap(ix->part_i, ix->alt_part_i);
-    std::swap(ix->cand, ix->alt_cand);
-    std::swap(ix->mbnd, ix->alt_mbnd);
-    std::swap(ix->mflag, ix->alt_mflag);
-    ix->cur_set ^= 1;
+void swap_scratch_sets(mips_index* ix) { std::swap(ix->cur, ix->alt); }
+
+// A tail of a split-tail search may still be reading its scratch set (staged queries, lists) and the stored rows from its tail
+// stream: what is enqueued on st from here on comes behind it.  both_sets: the other set's tail as well (calls that move rows)
+int wait_for_tail(mips_index* ix, hipStream_t st, bool both_sets) {
+    for (ScratchSet* s : {&ix->cur, &ix->alt}) {
+        if (s == &ix->alt && !both_sets) break;
+        if (s->tail_pending) {
+            HIP_TRY(hipStreamWaitEvent(st, s->tail_done, 0));
+            s->tail_pending = false;
+        }
+    }
+    return MIPS_OK;
+}
+
+// The pinned words a certifying search reads its counts back into
+int ensure_nflag_host(mips_index* ix) {
+    if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host.p, 64, hipHostMallocDefault));
+    return MIPS_OK;
+}
+
+// The stored rows from first_changed_row on changed (added, moved, gone): what is derived from them is computed again when next
+// needed -- the bf16 image of an fp32-exact index from that row on, phi unless it was set from outside, the row-norm bounds
+void rows_changed(mips_index* ix, int64_t first_changed_row) {
+    ix->hi_rows = std::min(ix->hi_rows, first_changed_row);
+    if (!ix->phi_override) ix->phi_valid = false;
+    ix->xmax2_valid = false;
+    ix->dres2_valid = false;
 }
 
 } // namespace

@@ -100,7 +100,7 @@ int stage_selector(mips_index* ix, Selector& sel, int64_t nq, hipStream_t st) {
 // packed: d_i is the MIPS_OUT_PACKED payload [nq][k][2] and d_s is not written (it may be NULL)
 // sel.bits != nullptr: a filtered search (masked scan, certificate on the selected count, masked settlement)
 // sel.qlab != nullptr: a grouped search (grouped scan, certificate without a count, settlement that tests the labels)
-int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool q_dev,
+int wide_search(mips_index* ix, SearchReport& rep, const void* q, int q_dtype, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, bool q_dev,
                 Selector sel, int metric, hipStream_t st) {
     const bool grouped = sel.qlab != nullptr;
     const bool masked = sel.bits != nullptr && !grouped;
@@ -195,23 +195,23 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         // ---- stage the slice's queries: canonical form (bf16 rows / fp32 rows) and, fp32-exact index, bf16(q) for the scan
         const int64_t nq_padq = query_pad(ix, ns);
         const size_t row_bytes = (size_t)ix->ld * ix->qsize;
-        rc = ix->qbuf.ensure((size_t)nq_padq * row_bytes);
+        rc = ix->cur.qbuf.ensure((size_t)nq_padq * row_bytes);
         if (rc) return rc;
         if (f32x) {
-            rc = ix->qf32.ensure((size_t)nq_padq * ix->plane * sizeof(float));
+            rc = ix->cur.qf32.ensure((size_t)nq_padq * ix->plane * sizeof(float));
             if (rc) return rc;
-            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->qbuf.p, st, (float*)ix->qf32.p);
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->cur.qbuf.p, st, (float*)ix->cur.qf32.p);
             if (rc) return rc;
             rc = ix->qhi.ensure((size_t)nq_padq * ix->hp * 2);
             if (rc) return rc;
             rc = ix->qerr2.ensure((size_t)ns * sizeof(double));
             if (rc) return rc;
-            mips::convert_rows_kernel<float><<<grid_for(nq_padq * (int64_t)(ix->hp / 8), 256), 256, 0, st>>>((const float*)ix->qf32.p, ns, ix->plane,
+            mips::convert_rows_kernel<float><<<grid_for(nq_padq * (int64_t)(ix->hp / 8), 256), 256, 0, st>>>((const float*)ix->cur.qf32.p, ns, ix->plane,
                                                                                                            (uint16_t*)ix->qhi.p, ix->hp, nq_padq);
-            mips::query_resid_kernel<<<(int)((ns + 3) / 4), 256, 0, st>>>((const float*)ix->qf32.p, ns, ix->plane, (double*)ix->qerr2.p);
+            mips::query_resid_kernel<<<(int)((ns + 3) / 4), 256, 0, st>>>((const float*)ix->cur.qf32.p, ns, ix->plane, (double*)ix->qerr2.p);
             HIP_TRY(hipGetLastError());
         } else {
-            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->qbuf.p, st, nullptr, nq_padq - ns, nullptr, 0, ix->qsize);
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev ? 1 : 0, (uint8_t*)ix->cur.qbuf.p, st, nullptr, nq_padq - ns, nullptr, 0, ix->qsize);
             if (rc) return rc;
         }
         mips::wide_init_kernel<<<(int)((ns_pad + 255) / 256), 256, 0, st>>>((int)ns, (int)ns_pad, w.pool_n, w.tau_c, w.tau_f);
@@ -220,8 +220,8 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         // ---- threshold scan + select, chunk by chunk (chunks double up to the budget: a pool's expected intake per chunk is
         // k' ln(rows after / rows before))
         mips::WideScanArgs sa;
-        sa.docs = f32x ? (const uint16_t*)ix->rows_hi : (const uint16_t*)ix->rows;
-        sa.qbuf = f32x ? (const uint16_t*)ix->qhi.p : (const uint16_t*)ix->qbuf.p;
+        sa.docs = f32x ? (const uint16_t*)ix->rows_hi.p : (const uint16_t*)ix->rows.p;
+        sa.qbuf = f32x ? (const uint16_t*)ix->qhi.p : (const uint16_t*)ix->cur.qbuf.p;
         sa.ntotal = ix->ntotal;
         sa.ld = sld;
         sa.ksteps = sld / mips::BK;
@@ -269,8 +269,8 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         ra.pool_stride = kp;
         ra.pool_n = w.pool_n;
         ra.kp = kp;
-        ra.rows = f32x ? (const void*)ix->rows_f32 : (const void*)ix->rows;
-        ra.y = f32x ? (const void*)ix->qf32.p : (const void*)ix->qbuf.p;
+        ra.rows = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
+        ra.y = f32x ? (const void*)ix->cur.qf32.p : (const void*)ix->cur.qbuf.p;
         ra.ld = cld;
         ra.ntotal = ix->ntotal;
         ra.k = k;
@@ -379,14 +379,11 @@ int wide_search(mips_index* ix, const void* q, int q_dtype, int64_t nq, int k, f
         }
     }
     set_kernel_name(ix, grouped ? "mips::grouped_scan_kernel" : masked ? "mips::masked_scan_kernel" : "mips::wide_scan_kernel");
-    // statistics: flagged = settled exactly; nothing is ever left unresolved
-    ix->last_flagged = -1; // (on the device: mips_index_margin_stats fetches the two words when asked)
-    ix->last_rescanned = 0;
-    ix->last_unresolved = 0;
-    ix->last_max_n = 0;
-    ix->last_fallback = false;
-    ix->first_nflag_dev = (const int*)w.words;
-    ix->last_nflag_dev = w.words + 1;
+    // the report: flagged = settled exactly; nothing is ever left unresolved.  (The counts stay on the device:
+    // mips_index_margin_stats fetches the two words when asked)
+    rep = SearchReport();
+    rep.first_dev = (const int*)w.words;
+    rep.last_dev = w.words + 1;
     return MIPS_OK;
 }
 

@@ -1,7 +1,8 @@
 // C ABI of the MI355X MIPS backend (include/mips_hip.h), gfx950 only.  ONE translation unit: the kernels (*.hpp), the host side
-// in three parts -- host_state.hpp (the index object), host_launch.hpp (which kernel answers which search), host_search.hpp (what a
-// search does around its scan) -- and, below, the extern "C" entry points themselves.  The search entry points validate their
-// arguments and then share one prologue (run_call), which hands their body the SearchCall of the whole index.
+// in three parts -- host_state.hpp (the index object; search_report.hpp: the report of a search call), host_launch.hpp (which kernel
+// answers which search), host_search.hpp (what a search does around its scan) -- and, below, the extern "C" entry points themselves.
+// The search entry points validate their arguments and then share one prologue (run_call), which hands their body the SearchCall
+// of the whole index and the call's SearchReport.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -35,6 +37,7 @@
 #include "remove_kernels.hpp"
 #include "rows_kernels.hpp"
 
+#include "search_report.hpp"
 #include "host_state.hpp"
 #include "host_launch.hpp"
 #include "host_search.hpp"
@@ -67,7 +70,8 @@ int mips_index_create(mips_index_t** out, int device, int64_t d, int doc_dtype, 
     if (device < 0 || device >= count) return fail(MIPS_E_INVALID, "mips_index_create: no HIP device %d (have %d)", device, count);
     DeviceGuard g(device);
     if (!g.ok) return fail(MIPS_E_HIP, "hipSetDevice(%d) failed", device);
-    mips_index* ix = new (std::nothrow) mips_index();
+    // (declared behind the device guard: a failure below frees what the index holds with its device still current)
+    std::unique_ptr<mips_index> ix(new (std::nothrow) mips_index());
     if (!ix) return fail(MIPS_E_NOMEM, "out of host memory");
     ix->device = device;
     ix->d = d;
@@ -90,28 +94,16 @@ int mips_index_create(mips_index_t** out, int device, int64_t d, int doc_dtype, 
     ix->doc_dtype = doc_dtype;
     ix->metric = metric;
     for (int e = 0; e < mips_index::kEvRing; ++e)
-        if (hipEventCreate(&ix->ev0[e]) != hipSuccess || hipEventCreate(&ix->ev1[e]) != hipSuccess) {
-            mips_index_destroy(ix);
-            return fail(MIPS_E_HIP, "hipEventCreate failed");
-        }
-    if (hipEventCreateWithFlags(&ix->busy, hipEventDisableTiming) != hipSuccess) {
-        mips_index_destroy(ix);
+        if (create_event(ix->ev0[e], true) != hipSuccess || create_event(ix->ev1[e], true) != hipSuccess) return fail(MIPS_E_HIP, "hipEventCreate failed");
+    if (create_event(ix->busy, false) != hipSuccess || create_event(ix->scan_done, false) != hipSuccess ||
+        create_event(ix->cur.tail_done, false) != hipSuccess || create_event(ix->alt.tail_done, false) != hipSuccess)
         return fail(MIPS_E_HIP, "hipEventCreate failed");
-    }
-    if (hipEventCreateWithFlags(&ix->scan_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ix->tail_done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ix->tail_done[1], hipEventDisableTiming) != hipSuccess) {
-        mips_index_destroy(ix);
-        return fail(MIPS_E_HIP, "hipEventCreate failed");
-    }
     // the sticky scan-error word: pinned host memory the device writes to (coherent, mapped)
-    if (hipHostMalloc((void**)&ix->sticky_host, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&ix->sticky_dev, ix->sticky_host, 0) != hipSuccess) {
-        mips_index_destroy(ix);
+    if (hipHostMalloc((void**)&ix->sticky_host.p, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&ix->sticky_dev, ix->sticky_host, 0) != hipSuccess)
         return fail(MIPS_E_HIP, "hipHostMalloc for the scan-error word failed");
-    }
     for (int w = 0; w < 16; ++w) ix->sticky_host[w] = 0u; // [0] scan error, [2..3] resolve statistics of the last stream-ordered search
-    *out = ix;
+    *out = ix.release();
     return MIPS_OK;
 }
 
@@ -119,70 +111,7 @@ int mips_index_destroy(mips_index_t* ix) {
     if (!ix) return MIPS_OK;
     DeviceGuard g(ix->device);
     (void)hipDeviceSynchronize();
-    if (ix->rows) (void)hipFree(ix->rows);
-    ix->qbuf.release();
-    ix->part_s.release();
-    ix->part_i.release();
-    ix->stage.release();
-    ix->out_s.release();
-    ix->out_i.release();
-    ix->scalar.release();
-    ix->gthr.release();
-    ix->cand.release();
-    ix->qf32.release();
-    ix->mbnd.release();
-    ix->mflag.release();
-    ix->qbuf2.release();
-    ix->qf32b.release();
-    ix->tmp_s.release();
-    ix->tmp_i.release();
-    ix->ids.release();
-    if (ix->xmax2_dev) (void)hipFree(ix->xmax2_dev);
-    if (ix->nflag_host) (void)hipHostFree(ix->nflag_host);
-    if (ix->tiny_words) (void)hipFree(ix->tiny_words);
-    if (ix->rows_f32) (void)hipFree(ix->rows_f32);
-    if (ix->rows_hi) (void)hipFree(ix->rows_hi);
-    if (ix->dres2_dev) (void)hipFree(ix->dres2_dev);
-    ix->qhi.release();
-    ix->qerr2.release();
-    ix->keyk.release();
-    ix->qqv.release();
-    ix->hit_d.release();
-    ix->hit_i.release();
-    ix->hit_n.release();
-    ix->qnorm.release();
-    ix->w_seg.release();
-    ix->w_pool.release();
-    ix->w_cnt.release();
-    ix->w_misc.release();
-    ix->r_stage.release();
-    ix->r_blk.release();
-    ix->r_misc.release();
-    ix->r_lims.release();
-    ix->sel_raw.release();
-    ix->sel_words.release();
-    ix->grp_q.release();
-    ix->row_ids.release();
-    ix->row_out.release();
-    if (ix->labels) (void)hipFree(ix->labels);
-    for (int e = 0; e < mips_index::kEvRing; ++e) {
-        if (ix->ev0[e]) (void)hipEventDestroy(ix->ev0[e]);
-        if (ix->ev1[e]) (void)hipEventDestroy(ix->ev1[e]);
-    }
-    if (ix->busy) (void)hipEventDestroy(ix->busy);
-    if (ix->scan_done) (void)hipEventDestroy(ix->scan_done);
-    for (int e = 0; e < 2; ++e)
-        if (ix->tail_done[e]) (void)hipEventDestroy(ix->tail_done[e]);
-    ix->alt_qbuf.release();
-    ix->alt_qf32.release();
-    ix->alt_gthr.release();
-    ix->alt_part_s.release();
-    ix->alt_part_i.release();
-    ix->alt_cand.release();
-    ix->alt_mbnd.release();
-    ix->alt_mflag.release();
-    if (ix->sticky_host) (void)hipHostFree(ix->sticky_host);
-    delete ix;
+    delete ix; // (every member that holds a device resource frees it: host_state.hpp)
     return MIPS_OK;
 }
 
@@ -209,10 +138,8 @@ int mips_index_add(mips_index_t* ix, const void* rows, int64_t n, int src_dtype,
     rc = convert_into(ix, rows, n, src_dtype, src_is_device, ix->rows + (size_t)ix->ntotal * ix->ld * ix->esize, st,
                       ix->plane > 0 ? ix->rows_f32 + (size_t)ix->ntotal * ix->plane : nullptr);
     if (rc) return rc;
+    rows_changed(ix, ix->ntotal);
     ix->ntotal += n;
-    if (!ix->phi_override) ix->phi_valid = false;
-    ix->xmax2_valid = false;
-    ix->dres2_valid = false;
     return MIPS_OK;
 }
 
@@ -220,11 +147,8 @@ int mips_index_reset(mips_index_t* ix) {
     if (!ix) return fail(MIPS_E_INVALID, "mips_index_reset: index is NULL");
     ix->ntotal = 0;
     ix->nlabelled = 0;
-    ix->hi_rows = 0;
-    ix->phi_valid = false;
     ix->phi_override = false;
-    ix->xmax2_valid = false;
-    ix->dres2_valid = false;
+    rows_changed(ix, 0);
     return MIPS_OK;
 }
 
@@ -241,19 +165,15 @@ int mips_index_set_labels(mips_index_t* ix, const int32_t* labels, int64_t row0,
     ORDER_ON(ix, st);
     const int64_t need = round_up(std::max(ix->capacity, ix->ntotal), mips::TM); // whole tiles: the grouped scan loads a tile's labels
     if (ix->labels_cap < need) {
-        int* fresh = nullptr;
-        hipError_t e = hipMalloc((void**)&fresh, (size_t)need * sizeof(int));
+        DeviceArray<int> fresh; // (swapped in below: the old storage goes with it when the block ends, behind the synchronisation)
+        hipError_t e = hipMalloc((void**)&fresh.p, (size_t)need * sizeof(int));
         if (e != hipSuccess) return fail(MIPS_E_NOMEM, "hipMalloc(%zu) for the row labels failed: %s", (size_t)need * sizeof(int), hipGetErrorString(e));
         e = hipMemsetAsync(fresh, 0, (size_t)need * sizeof(int), st);
         if (e == hipSuccess && ix->nlabelled > 0)
             e = hipMemcpyAsync(fresh, ix->labels, (size_t)ix->nlabelled * sizeof(int), hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess && ix->labels) e = hipStreamSynchronize(st); // the old storage is freed below
-        if (e != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(MIPS_E_HIP, "growing the row labels to %lld rows failed: %s", (long long)need, hipGetErrorString(e));
-        }
-        if (ix->labels) (void)hipFree(ix->labels);
-        ix->labels = fresh;
+        if (e == hipSuccess && ix->labels) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(MIPS_E_HIP, "growing the row labels to %lld rows failed: %s", (long long)need, hipGetErrorString(e));
+        std::swap(ix->labels, fresh);
         ix->labels_cap = need;
     }
     HIP_TRY(hipMemcpyAsync(ix->labels + row0, labels, (size_t)n * sizeof(int), src_is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
@@ -344,10 +264,8 @@ int mips_index_add_synthetic(mips_index_t* ix, int64_t n, int64_t row0, uint64_t
                                                                       (int)ix->d, ix->ld, row0, seed, kind, ix->esize == 1 ? 2 : 0);
     }
     HIP_TRY(hipGetLastError());
+    rows_changed(ix, ix->ntotal); // (as mips_index_add: a phi set from outside stays until the caller renews it)
     ix->ntotal += n;
-    if (!ix->phi_override) ix->phi_valid = false; // as mips_index_add: an override stays until the caller renews it
-    ix->xmax2_valid = false;
-    ix->dres2_valid = false;
     return MIPS_OK;
 }
 
@@ -390,7 +308,8 @@ SearchCall index_call(const mips_index* ix, int flags) {
 // synchronisation: the word lives in host memory) before anything new is enqueued; order the call behind the last one on
 // another stream; split-tail form: take the other scratch set, so that this scan may run while the previous search's tail still
 // reads its lists; whichever set is about to be used, a tail still pending on it (it reads the set's staged queries) comes
-// first.  body(c) is the rest of the call.
+// first.  body(c, rep) is the rest of the call; it fills in the call's report, which becomes the index's when the call
+// succeeds -- until then, and after an error, the index reports "unknown".
 template <class Body>
 int run_call(const char* who, mips_index* ix, int flags, hipStream_t st, bool split, Body body) {
     DeviceGuard g(ix->device);
@@ -398,12 +317,14 @@ int run_call(const char* who, mips_index* ix, int flags, hipStream_t st, bool sp
     if (prev) return prev;
     ORDER_ON(ix, st);
     if (split) swap_scratch_sets(ix);
-    if (ix->tail_pending[ix->cur_set]) {
-        HIP_TRY(hipStreamWaitEvent(st, ix->tail_done[ix->cur_set], 0));
-        ix->tail_pending[ix->cur_set] = false;
-    }
+    int rc = wait_for_tail(ix, st, /*both_sets=*/false);
+    if (rc) return rc;
+    ix->report = SearchReport();
     SearchCall c = index_call(ix, flags);
-    return body(c);
+    SearchReport rep;
+    rc = body(c, rep);
+    if (rc == MIPS_OK) ix->report = rep;
+    return rc;
 }
 
 // Host-output calls compute into the index's own device buffers (n scores and indices), copied out when the call ends
@@ -419,7 +340,7 @@ int device_outputs(mips_index* ix, bool out_dev, int64_t n, float*& d_s, int64_t
 }
 
 // mips_search / mips_search_split behind run_call: the one-launch kernel or stage queries -> pool_policy -> scan_and_finish<K'>
-int search_call(mips_index* ix, SearchCall& c, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx, int64_t idx_offset,
+int search_call(mips_index* ix, SearchCall& c, SearchReport& rep, const void* q, int q_dtype, int64_t nq, int k, float* out_scores, int64_t* out_idx, int64_t idx_offset,
                 int flags, hipStream_t st, hipStream_t tail_st) {
     const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
     const bool packed = (flags & MIPS_OUT_PACKED) != 0;
@@ -439,6 +360,7 @@ int search_call(mips_index* ix, SearchCall& c, const void* q, int q_dtype, int64
         const int64_t total = nq * k;
         mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, packed ? d_i : nullptr, total, c.metric);
         HIP_TRY(hipGetLastError());
+        rep = SearchReport::all_certified();
     } else if (tiny_eligible(ix, nq, k, certifies)) {
         // the reference's own call shape (<= 16 queries, small knowledge base): one launch (tiny_search.hpp)
         const void* qd = q;
@@ -449,13 +371,13 @@ int search_call(mips_index* ix, SearchCall& c, const void* q, int q_dtype, int64
             HIP_TRY(hipMemcpyAsync(ix->stage.p, q, qbytes, hipMemcpyHostToDevice, st));
             qd = ix->stage.p;
         }
-        rc = tiny_search(ix, c, qd, q_dtype, nq, k, k, 0, nullptr, d_s, d_i, packed, idx_offset, st, certifies);
+        rc = tiny_search(ix, c, qd, q_dtype, nq, k, k, 0, nullptr, d_s, d_i, packed, idx_offset, st, certifies, &rep.last_dev);
         if (rc) return rc;
         if (certifies) {
             // the exact pass behind the one launch (the kernel, and with it its results, live on the scan stream even in the
             // split-tail form).  Device outputs: enqueued blind, it leaves at once when nothing was flagged; host buffers and
             // "margin_check" = 2 synchronise, read the count and skip it when that is 0
-            rc = resolve_flagged(ix, c, nq, k, d_s, d_i, packed, idx_offset, st, /*certify_now=*/!(out_dev && c.margin == 3), /*skip_compact=*/true);
+            rc = resolve_flagged(ix, c, rep, nq, k, d_s, d_i, packed, idx_offset, st, /*certify_now=*/!(out_dev && c.margin == 3), /*skip_compact=*/true);
             if (rc < 0) return rc; // (kUseRescan cannot happen: <= 16 queries)
         }
     } else {
@@ -463,34 +385,34 @@ int search_call(mips_index* ix, SearchCall& c, const void* q, int q_dtype, int64
         // fp32-exact index next to them; the scan's shared insert bounds (8 class words per query + the error word) cleared
         const int64_t nq_pad = query_pad(ix, nq);
         const size_t row_bytes = (size_t)ix->ld * ix->qsize;
-        rc = ix->qbuf.ensure((size_t)nq_pad * row_bytes);
+        rc = ix->cur.qbuf.ensure((size_t)nq_pad * row_bytes);
         if (rc) return rc;
-        uint8_t* qb = (uint8_t*)ix->qbuf.p;
+        uint8_t* qb = (uint8_t*)ix->cur.qbuf.p;
         const int64_t thr_words = nq_pad * 8 + 4;
-        rc = ix->gthr.ensure((size_t)thr_words * sizeof(unsigned));
+        rc = ix->cur.gthr.ensure((size_t)thr_words * sizeof(unsigned));
         if (rc) return rc;
         if (ix->plane > 0) { // fp32-exact staging has its own kernel: clear with plain memsets
-            rc = ix->qf32.ensure((size_t)nq_pad * ix->plane * sizeof(float));
+            rc = ix->cur.qf32.ensure((size_t)nq_pad * ix->plane * sizeof(float));
             if (rc) return rc;
-            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, (float*)ix->qf32.p);
+            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, (float*)ix->cur.qf32.p);
             if (rc) return rc;
             if (nq_pad > nq) HIP_TRY(hipMemsetAsync(qb + (size_t)nq * row_bytes, 0, (size_t)(nq_pad - nq) * row_bytes, st));
-            HIP_TRY(hipMemsetAsync(ix->gthr.p, 0, (size_t)thr_words * sizeof(unsigned), st));
+            HIP_TRY(hipMemsetAsync(ix->cur.gthr.p, 0, (size_t)thr_words * sizeof(unsigned), st));
         } else { // one launch converts the queries, zero-pads to the tile multiple and clears the bounds
-            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, nullptr, nq_pad - nq, (uint32_t*)ix->gthr.p, thr_words, ix->qsize);
+            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, nullptr, nq_pad - nq, (uint32_t*)ix->cur.gthr.p, thr_words, ix->qsize);
             if (rc) return rc;
         }
-        c.qbuf = ix->qbuf.p;
-        c.qf32 = ix->qf32.p;
+        c.qbuf = ix->cur.qbuf.p;
+        c.qf32 = ix->cur.qf32.p;
         const PoolPolicy pol = pool_policy(ix, nq, k, out_dev, split, c.margin);
         if (pol.fast) { // bf16(q) at the bf16 kernels' row pitch, |q - bf16 q|^2, bf16 rows and residual bound up to date
             rc = ix->qhi.ensure((size_t)nq_pad * ix->hp * 2);
             if (rc) return rc;
             rc = ix->qerr2.ensure((size_t)nq * sizeof(double));
             if (rc) return rc;
-            mips::convert_rows_kernel<float><<<grid_for(nq_pad * (int64_t)(ix->hp / 8), 256), 256, 0, st>>>((const float*)ix->qf32.p, nq, ix->plane,
+            mips::convert_rows_kernel<float><<<grid_for(nq_pad * (int64_t)(ix->hp / 8), 256), 256, 0, st>>>((const float*)ix->cur.qf32.p, nq, ix->plane,
                                                                                                            (uint16_t*)ix->qhi.p, ix->hp, nq_pad);
-            mips::query_resid_kernel<<<(int)((nq + 3) / 4), 256, 0, st>>>((const float*)ix->qf32.p, nq, ix->plane, (double*)ix->qerr2.p);
+            mips::query_resid_kernel<<<(int)((nq + 3) / 4), 256, 0, st>>>((const float*)ix->cur.qf32.p, nq, ix->plane, (double*)ix->qerr2.p);
             HIP_TRY(hipGetLastError());
             rc = ensure_hi(ix, st);
             if (rc) return rc;
@@ -498,10 +420,10 @@ int search_call(mips_index* ix, SearchCall& c, const void* q, int q_dtype, int64
             if (rc) return rc;
         }
         switch (pol.kl) {
-        case 8: rc = scan_and_finish<8>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
-        case 10: rc = scan_and_finish<10>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
-        case 16: rc = scan_and_finish<16>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
-        default: rc = scan_and_finish<32>(ix, c, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
+        case 8: rc = scan_and_finish<8>(ix, c, rep, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
+        case 10: rc = scan_and_finish<10>(ix, c, rep, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
+        case 16: rc = scan_and_finish<16>(ix, c, rep, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
+        default: rc = scan_and_finish<32>(ix, c, rep, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
         }
         if (rc) return rc;
     }
@@ -526,8 +448,8 @@ int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k,
     if (!q || !out_idx || (!out_scores && !(flags & MIPS_OUT_PACKED))) return fail(MIPS_E_INVALID, "mips_search: NULL buffer");
     if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_search: more than 2^24 queries in one call");
     const hipStream_t st = (hipStream_t)hip_stream, tail_st = (hipStream_t)tail_stream;
-    return run_call("mips_search", ix, flags, st, tail_st != st, [&](SearchCall& c) {
-        return search_call(ix, c, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, st, tail_st);
+    return run_call("mips_search", ix, flags, st, tail_st != st, [&](SearchCall& c, SearchReport& rep) {
+        return search_call(ix, c, rep, q, q_dtype, nq, k, out_scores, out_idx, idx_offset, flags, st, tail_st);
     });
 }
 
@@ -580,7 +502,7 @@ int search_wide_impl(const char* who, mips_index_t* ix, const void* q, int q_dty
     if (!q || !out_idx || (!out_scores && !packed)) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
     if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "%s: more than 2^24 queries in one call", who);
     const hipStream_t st = (hipStream_t)hip_stream;
-    return run_call(who, ix, flags, st, false, [&](SearchCall& c) {
+    return run_call(who, ix, flags, st, false, [&](SearchCall& c, SearchReport& rep) {
         float* d_s = out_scores;
         int64_t* d_i = out_idx;
         int rc = device_outputs(ix, out_dev, nq * k, d_s, d_i);
@@ -589,23 +511,21 @@ int search_wide_impl(const char* who, mips_index_t* ix, const void* q, int q_dty
             const int64_t total = nq * k;
             mips::fill_empty_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(d_s, d_i, packed ? d_i : nullptr, total, c.metric);
             HIP_TRY(hipGetLastError());
-            ix->last_flagged = 0;
-            ix->last_rescanned = 0;
-            ix->last_unresolved = 0;
-            ix->first_nflag_dev = nullptr;
+            rep = SearchReport::all_certified();
         } else {
-            rc = wide_search(ix, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, c.metric, st);
+            rc = wide_search(ix, rep, q, q_dtype, nq, k, d_s, d_i, packed, idx_offset, (flags & MIPS_Q_DEVICE) != 0, sel, c.metric, st);
             if (rc) return rc;
         }
         if (!out_dev) {
-            if (!ix->nflag_host) HIP_TRY(hipHostMalloc((void**)&ix->nflag_host, 64, hipHostMallocDefault));
+            rc = ensure_nflag_host(ix);
+            if (rc) return rc;
             HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-            if (ix->ntotal > 0) HIP_TRY(hipMemcpyAsync(ix->nflag_host, ix->first_nflag_dev, 4, hipMemcpyDeviceToHost, st));
+            if (rep.first_dev) HIP_TRY(hipMemcpyAsync(ix->nflag_host, rep.first_dev, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if (ix->ntotal > 0) {
-                ix->last_flagged = (int64_t)ix->nflag_host[0];
-                ix->last_rescanned = ix->last_flagged;
+            if (rep.first_dev) { // (the stream is drained: the flagged count is known, and every flagged query was settled)
+                rep.flagged = (int64_t)ix->nflag_host[0];
+                rep.rescanned = rep.settled();
             }
         }
         return (int)MIPS_OK;
@@ -629,7 +549,7 @@ int range_search_impl(const char* who, mips_index_t* ix, const void* q, int q_dt
         if (radii[j] != radii[j]) return fail(MIPS_E_INVALID, "%s: radii[%lld] is NaN", who, (long long)j);
     const bool out_dev = (flags & MIPS_OUT_DEVICE) != 0;
     const hipStream_t st = (hipStream_t)hip_stream;
-    return run_call(who, ix, flags, st, false, [&](SearchCall& c) {
+    return run_call(who, ix, flags, st, false, [&](SearchCall& c, SearchReport& rep) {
         int64_t* d_lims = out_lims;
         float* d_s = out_scores;
         int64_t* d_i = out_idx;
@@ -647,12 +567,7 @@ int range_search_impl(const char* who, mips_index_t* ix, const void* q, int q_dt
             if (rc) return rc;
         }
         // nothing is ever uncertified: the candidates are a provable superset and the filter decides on the canonical score
-        ix->last_flagged = 0;
-        ix->last_rescanned = 0;
-        ix->last_unresolved = 0;
-        ix->last_max_n = 0;
-        ix->last_fallback = false;
-        ix->first_nflag_dev = nullptr;
+        rep = SearchReport::all_certified();
         if (!out_dev) {
             HIP_TRY(hipMemcpyAsync(out_lims, d_lims, (size_t)(nq + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
             if (cap > 0) {
@@ -736,8 +651,10 @@ int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64
         if (prev) return prev;
     }
     ORDER_ON(ix, st);
+    ix->report = SearchReport(); // (as run_call: "unknown" until a form below has succeeded)
     {
         SearchCall c = index_call(ix, MIPS_OUT_DEVICE);
+        SearchReport rep;
         const bool certifies = call_certifies(c.margin, /*out_dev=*/true);
         if (tiny_eligible(ix, nq, k_fetch, certifies)) {
             if (c.metric == MIPS_METRIC_L2) {
@@ -745,15 +662,17 @@ int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64
                 if (rc) return rc;
             }
             int rc = tiny_search(ix, c, q_device, q_dtype, nq, k_fetch, k, normalize, ignore_device, out_scores_device, out_idx_device, false,
-                                 idx_offset, st, certifies);
+                                 idx_offset, st, certifies, &rep.last_dev);
             if (rc) return rc;
-            if (!certifies) return MIPS_OK; // ("margin_check" = 4 / 0: flagged queries are counted, or not even that)
             // certified: the exact pass behind the one launch ranks the hits of a flagged query and applies the same ignore
             // filter -- without a synchronisation by default (it leaves at once when nothing was flagged); "margin_check" = 2
-            // synchronises to read the counts
-            rc = resolve_flagged(ix, c, nq, k_fetch, out_scores_device, out_idx_device, false, idx_offset, st, /*certify_now=*/c.margin == 2,
-                                 /*skip_compact=*/true, ignore_device, k);
-            return rc < 0 ? rc : MIPS_OK;
+            // synchronises to read the counts.  ("margin_check" = 4 / 0: flagged queries are counted, or not even that)
+            if (certifies)
+                rc = resolve_flagged(ix, c, rep, nq, k_fetch, out_scores_device, out_idx_device, false, idx_offset, st, /*certify_now=*/c.margin == 2,
+                                     /*skip_compact=*/true, ignore_device, k);
+            if (rc < 0) return rc;
+            ix->report = rep;
+            return MIPS_OK;
         }
     }
     // general form: the same steps as separate launches
@@ -1047,8 +966,8 @@ int mips_index_check_error(mips_index_t* ix, int synchronize, void* hip_stream) 
     if (synchronize) {
         DeviceGuard g(ix->device);
         HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
-        for (int e = 0; e < 2; ++e) // split-tail searches raise the sticky word from their tail stream
-            if (ix->tail_pending[e]) HIP_TRY(hipEventSynchronize(ix->tail_done[e]));
+        for (ScratchSet* s : {&ix->cur, &ix->alt}) // split-tail searches raise the sticky word from their tail stream
+            if (s->tail_pending) HIP_TRY(hipEventSynchronize(s->tail_done));
     }
     return take_scan_error(ix, "mips_index_check_error");
 }
@@ -1058,34 +977,23 @@ const char* mips_index_last_kernel(const mips_index_t* ix) { return ix ? ix->las
 int mips_index_margin_stats(mips_index_t* ix, int64_t* flagged, int64_t* rescanned, int64_t* unresolved, int synchronize,
                             void* hip_stream) {
     if (!ix) return fail(MIPS_E_INVALID, "mips_index_margin_stats: index is NULL");
-    if (synchronize && ix->tail_pending[ix->cur_set]) { // a split-tail search writes its counters on the tail stream
+    SearchReport& r = ix->report;
+    if (synchronize && ix->cur.tail_pending) { // a split-tail search writes its counters on the tail stream
         DeviceGuard g(ix->device);
-        HIP_TRY(hipEventSynchronize(ix->tail_done[ix->cur_set]));
+        HIP_TRY(hipEventSynchronize(ix->cur.tail_done));
     }
-    if (ix->last_flagged < 0 && synchronize && ix->first_nflag_dev != nullptr) {
-        // the last search re-scanned its flagged queries on the stream: first count = flagged = re-scanned, second = unresolved
+    if (r.flagged < 0 && synchronize && r.last_dev != nullptr) {
+        // the last search left its counts on the device (search_report.hpp): fetch the one or two words now
         DeviceGuard g(ix->device);
         unsigned n[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(&n[0], ix->first_nflag_dev, 4, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        HIP_TRY(hipMemcpyAsync(&n[1], ix->last_nflag_dev, 4, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+        if (r.first_dev) HIP_TRY(hipMemcpyAsync(&n[0], r.first_dev, 4, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
+        HIP_TRY(hipMemcpyAsync(&n[1], r.last_dev, 4, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
         HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
-        ix->last_flagged = (int64_t)n[0];
-        ix->last_unresolved = (int64_t)n[1];
-        // settled exactly (or re-scanned by the fall-back); a search over its budget whose first results stand settled nothing
-        ix->last_rescanned = (ix->last_max_n > 0 && (int64_t)n[0] > ix->last_max_n && !ix->last_fallback) ? 0 : (int64_t)n[0];
-    } else if (ix->last_flagged < 0 && synchronize && ix->opt_margin != 0 && ix->last_nflag_dev != nullptr) {
-        // the last search only counted on the device: fetch the count now
-        DeviceGuard g(ix->device);
-        unsigned n = 0;
-        HIP_TRY(hipMemcpyAsync(&n, ix->last_nflag_dev, 4, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));
-        HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));
-        ix->last_flagged = (int64_t)n;
-        ix->last_rescanned = 0;
-        ix->last_unresolved = (int64_t)n;
+        r.read_back(n[0], n[1]);
     }
-    if (flagged) *flagged = ix->last_flagged;
-    if (rescanned) *rescanned = ix->last_rescanned;
-    if (unresolved) *unresolved = ix->last_unresolved;
+    if (flagged) *flagged = r.flagged;
+    if (rescanned) *rescanned = r.rescanned;
+    if (unresolved) *unresolved = r.unresolved;
     return MIPS_OK;
 }
 
