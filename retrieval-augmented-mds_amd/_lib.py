@@ -21,6 +21,7 @@ HEADER = os.path.join(_ROOT, "include", "mips_hip.h")
 HEADER_SHARDED = os.path.join(_ROOT, "include", "mips_hip_sharded.h")  # helpers of the shard exchange (no index handle)
 HEADER_UPDATE = os.path.join(_ROOT, "include", "mips_hip_update.h")  # calls that change the rows an index holds
 HEADER_ROWS = os.path.join(_ROOT, "include", "mips_hip_rows.h")  # stored rows, labels and scores by row id
+HEADER_HOOK = os.path.join(_ROOT, "include", "mips_hip_hook.h")  # the one-launch hook search under a group filter
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -41,7 +42,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -149,7 +150,10 @@ def _bind(lib):
         "mips_index_gather_labels": (i32, [vp, vp, i64, i64, vp, i32, vp]),
         "mips_score_subset": (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i32, vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows}.items():
+    sig_hook = {  # include/mips_hip_hook.h
+        "mips_search_fused_grp": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp, i64, vp, i32, i32, vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -171,6 +175,7 @@ EXPORTS = (
 EXPORTS_SHARDED = ("mips_range_merge_records",)  # what include/mips_hip_sharded.h declares; the same library exports it
 EXPORTS_UPDATE = ("mips_index_remove",)  # what include/mips_hip_update.h declares; the same library exports it
 EXPORTS_ROWS = ("mips_index_reconstruct", "mips_index_gather_labels", "mips_score_subset")  # include/mips_hip_rows.h, likewise
+EXPORTS_HOOK = ("mips_search_fused_grp",)  # include/mips_hip_hook.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:

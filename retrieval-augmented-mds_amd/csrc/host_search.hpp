@@ -38,8 +38,11 @@ int ensure_resolve_buffers(mips_index* ix, int64_t nq) {
 // handoff: prepare the stream-ordered exact pass (resolve_flagged with skip_compact) -- the kernel's last workgroup writes
 // the flag list, clears the hit counters and copies the staged queries out when something was flagged (c.qbuf / c.qf32: where to).
 // *nflag_dev: where the kernel counts the queries it flags (nullptr: the margin check is off)
+// qlab_dev != nullptr: the grouped form (mips_search_fused_grp) -- [nq] query labels on the device, tested against the index's
+// row labels; hook_grouped_kernel instead of tiny_search_kernel
 int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, int64_t nq, int k_fetch, int k_out, int normalize, const int64_t* ignore_dev,
-                float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool handoff, unsigned** nflag_dev) {
+                float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool handoff, unsigned** nflag_dev,
+                const int* qlab_dev = nullptr, int grp_only = 0) {
     const bool f32x = ix->plane > 0;
     const int tld = f32x ? ix->hp : ix->ld; // row pitch of the scanned bf16 rows
     if (f32x) { // bf16 rows + residual bound up to date, max |x|^2 on the fp32 rows
@@ -79,6 +82,13 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
     a.out_s = d_s;
     a.out_i = d_i;
     a.out_packed = packed ? d_i : nullptr;
+    a.rlab = nullptr;
+    a.qlab = qlab_dev;
+    a.grp_only = grp_only;
+    if (qlab_dev != nullptr) { // (a lane loads the four labels of its rows of a 16-row tile: the storage covers whole tiles)
+        if (ix->labels_cap < (int64_t)ntiles * 16) return fail(MIPS_E_INVALID, "tiny_search: the row labels do not cover the index (mips_index_set_labels)");
+        a.rlab = ix->labels;
+    }
     const size_t ncand = (size_t)nwg * mips::TINY_POOL; // per query: the 8 best of every workgroup
     int rc = ix->cur.part_s.ensure(16 * (ncand + nwg) * sizeof(float)); // + the workgroups' bounds behind the candidates
     if (rc) return rc;
@@ -148,11 +158,15 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
         return MIPS_OK;
     };
     const bool l2m = c.metric == MIPS_METRIC_L2;
-    if (f32x) rc = l2m ? go(mips::tiny_search_kernel<true, true>) : go(mips::tiny_search_kernel<false, true>);
+    const bool grp = qlab_dev != nullptr;
+    if (grp) {
+        if (f32x) rc = l2m ? go(mips::hook_grouped_kernel<true, true>) : go(mips::hook_grouped_kernel<false, true>);
+        else rc = l2m ? go(mips::hook_grouped_kernel<true, false>) : go(mips::hook_grouped_kernel<false, false>);
+    } else if (f32x) rc = l2m ? go(mips::tiny_search_kernel<true, true>) : go(mips::tiny_search_kernel<false, true>);
     else rc = l2m ? go(mips::tiny_search_kernel<true, false>) : go(mips::tiny_search_kernel<false, false>);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
-    set_kernel_name(ix, "mips::tiny_search_kernel<%s, %s>", l2m ? "true" : "false", f32x ? "true" : "false");
+    set_kernel_name(ix, grp ? "mips::hook_grouped_kernel<%s, %s>" : "mips::tiny_search_kernel<%s, %s>", l2m ? "true" : "false", f32x ? "true" : "false");
     return MIPS_OK;
 }
 
@@ -165,8 +179,9 @@ int tiny_search(mips_index* ix, SearchCall& c, const void* q_dev, int q_dtype, i
 constexpr int kUseRescan = 1;
 // skip_compact: the flag list, its count and the cleared counters are already on the device (the one-launch kernel's hand-off).
 // ignore / k_out: the fused hook call's ignore filter (ResolveArgs), d_s / d_i then are [nq][k_out].
+// qlab_dev / grp_only: the flagging search was the grouped hook call -- the same rule decides what becomes a hit.
 int resolve_flagged(mips_index* ix, const SearchCall& c, SearchReport& rep, int64_t nq, int k, float* d_s, int64_t* d_i, bool packed, int64_t idx_offset, hipStream_t st, bool certify_now,
-                    bool skip_compact = false, const int64_t* ignore = nullptr, int k_out = 0) {
+                    bool skip_compact = false, const int64_t* ignore = nullptr, int k_out = 0, const int* qlab_dev = nullptr, int grp_only = 0) {
     if (k > mips::RESOLVE_OVF_K) return fail(MIPS_E_UNSUPPORTED, "resolve_flagged: k = %d exceeds RESOLVE_OVF_K", k);
     int rc = ensure_resolve_buffers(ix, nq); // (never reallocates behind a hand-off: same sizes as tiny_search asked for)
     if (rc) return rc;
@@ -210,6 +225,11 @@ int resolve_flagged(mips_index* ix, const SearchCall& c, SearchReport& rep, int6
     a.unresolved = unres;
     a.ignore = ignore;
     a.k_out = ignore ? k_out : 0;
+    if (qlab_dev != nullptr) {
+        a.rlab = ix->labels;
+        a.qlab = qlab_dev;
+        a.grp_only = grp_only;
+    }
     int lds = mips::RESOLVE_QB * a.ld * (int)sizeof(double) + mips::RESOLVE_WAVES * 64 * 9 * 16;
     const int rows_per_wg = 64 * mips::RESOLVE_WAVES;
     int grid = (int)std::max<int64_t>(1, std::min<int64_t>(1024, (ix->ntotal + rows_per_wg - 1) / rows_per_wg));

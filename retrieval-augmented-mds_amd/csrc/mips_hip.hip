@@ -20,6 +20,7 @@
 #include "../../include/mips_hip_sharded.h"
 #include "../../include/mips_hip_update.h"
 #include "../../include/mips_hip_rows.h"
+#include "../../include/mips_hip_hook.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -633,21 +634,31 @@ int mips_range_search_grp(mips_index_t* ix, const void* q, int q_dtype, int64_t 
                              idx_offset, flags, sel_bits, sel_nbits, sel_bit0, hip_stream, q_labels, grp_mode);
 }
 
-int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64_t nq, int k, int normalize, const int64_t* ignore_device,
-                      float* out_scores_device, int64_t* out_idx_device, int64_t idx_offset, void* hip_stream) {
-    if (!ix) return fail(MIPS_E_INVALID, "mips_search_fused: index is NULL");
-    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_search_fused: negative nq or k");
+// mips_search_fused and, with q_labels, mips_search_fused_grp (include/mips_hip_hook.h): q_labels == nullptr is the ungrouped call,
+// grp_mode and flags are not looked at then
+static int search_fused_impl(const char* who, mips_index_t* ix, const void* q_device, int q_dtype, int64_t nq, int k, int normalize,
+                             const int64_t* ignore_device, float* out_scores_device, int64_t* out_idx_device, int64_t idx_offset,
+                             const int32_t* q_labels, int grp_mode, int flags, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "%s: index is NULL", who);
+    if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "%s: negative nq or k", who);
     const int k_fetch = k + (ignore_device ? 1 : 0);
-    if (k_fetch > MIPS_MAX_K) return fail(MIPS_E_UNSUPPORTED, "mips_search_fused: k = %d exceeds MIPS_MAX_K = %d", k_fetch, MIPS_MAX_K);
-    if (!src_dtype_ok(ix, q_dtype, true)) return fail(MIPS_E_INVALID, "mips_search_fused: q_dtype must be F32 or BF16");
-    if (normalize && q_dtype != MIPS_DTYPE_F32) return fail(MIPS_E_INVALID, "mips_search_fused: normalize needs float32 queries");
+    if (k_fetch > MIPS_MAX_K) return fail(MIPS_E_UNSUPPORTED, "%s: k = %d exceeds MIPS_MAX_K = %d", who, k_fetch, MIPS_MAX_K);
+    if (!src_dtype_ok(ix, q_dtype, true)) return fail(MIPS_E_INVALID, "%s: q_dtype must be F32 or BF16", who);
+    if (normalize && q_dtype != MIPS_DTYPE_F32) return fail(MIPS_E_INVALID, "%s: normalize needs float32 queries", who);
+    Selector sel;
+    if (q_labels) { // what the wide search refuses is refused here, whichever form would serve the call
+        int rc = check_served(who, ix, q_dtype);
+        if (rc) return rc;
+        rc = make_selector(who, ix, flags, nullptr, 0, 0, q_labels, grp_mode, sel);
+        if (rc) return rc;
+    }
     if (nq == 0 || k == 0) return MIPS_OK;
-    if (!q_device || !out_idx_device || !out_scores_device) return fail(MIPS_E_INVALID, "mips_search_fused: NULL buffer");
+    if (!q_device || !out_idx_device || !out_scores_device) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
     DeviceGuard g(ix->device);
     hipStream_t st = (hipStream_t)hip_stream;
     {   // (both forms below touch the index's scratch: an earlier scan error is reported, and a call on another stream ordered,
         // before anything is enqueued)
-        const int prev = take_scan_error(ix, "mips_search_fused");
+        const int prev = take_scan_error(ix, who);
         if (prev) return prev;
     }
     ORDER_ON(ix, st);
@@ -661,15 +672,25 @@ int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64
                 int rc = compute_phi(ix, st);
                 if (rc) return rc;
             }
+            const int* qlab_dev = nullptr; // the query labels on the device: the caller's, or a host array staged as stage_selector does
+            if (q_labels) {
+                qlab_dev = (const int*)q_labels;
+                if (!sel.qlab_dev) {
+                    int rc = ix->grp_q.ensure((size_t)nq * sizeof(int));
+                    if (rc) return rc;
+                    HIP_TRY(hipMemcpyAsync(ix->grp_q.p, q_labels, (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+                    qlab_dev = (const int*)ix->grp_q.p;
+                }
+            }
             int rc = tiny_search(ix, c, q_device, q_dtype, nq, k_fetch, k, normalize, ignore_device, out_scores_device, out_idx_device, false,
-                                 idx_offset, st, certifies, &rep.last_dev);
+                                 idx_offset, st, certifies, &rep.last_dev, qlab_dev, sel.grp_only);
             if (rc) return rc;
             // certified: the exact pass behind the one launch ranks the hits of a flagged query and applies the same ignore
             // filter -- without a synchronisation by default (it leaves at once when nothing was flagged); "margin_check" = 2
             // synchronises to read the counts.  ("margin_check" = 4 / 0: flagged queries are counted, or not even that)
             if (certifies)
                 rc = resolve_flagged(ix, c, rep, nq, k_fetch, out_scores_device, out_idx_device, false, idx_offset, st, /*certify_now=*/c.margin == 2,
-                                     /*skip_compact=*/true, ignore_device, k);
+                                     /*skip_compact=*/true, ignore_device, k, qlab_dev, sel.grp_only);
             if (rc < 0) return rc;
             ix->report = rep;
             return MIPS_OK;
@@ -686,17 +707,36 @@ int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64
         if (rc) return rc;
         qsrc = ix->qnorm.p;
     }
-    if (!ignore_device)
-        return mips_search(ix, qsrc, q_dtype, nq, k, out_scores_device, out_idx_device, idx_offset, MIPS_Q_DEVICE | MIPS_OUT_DEVICE, hip_stream);
+    // (grouped: the wide search under the same rule -- exact like the one launch, so the two forms agree bit for bit)
+    const int oflags = MIPS_Q_DEVICE | MIPS_OUT_DEVICE;
+    auto nested = [&](int kk, float* os, int64_t* oi) -> int {
+        if (q_labels)
+            return mips_search_wide_grp(ix, qsrc, q_dtype, nq, kk, os, oi, idx_offset, oflags | (flags & MIPS_GRP_DEVICE), nullptr, 0, 0, q_labels, grp_mode,
+                                        hip_stream);
+        return mips_search(ix, qsrc, q_dtype, nq, kk, os, oi, idx_offset, oflags, hip_stream);
+    };
+    if (!ignore_device) return nested(k, out_scores_device, out_idx_device);
     int rc = ix->out_s.ensure((size_t)nq * k_fetch * sizeof(float));
     if (rc) return rc;
     rc = ix->out_i.ensure((size_t)nq * k_fetch * sizeof(int64_t));
     if (rc) return rc;
-    rc = mips_search(ix, qsrc, q_dtype, nq, k_fetch, (float*)ix->out_s.p, (int64_t*)ix->out_i.p, idx_offset, MIPS_Q_DEVICE | MIPS_OUT_DEVICE,
-                     hip_stream);
+    rc = nested(k_fetch, (float*)ix->out_s.p, (int64_t*)ix->out_i.p);
     if (rc) return rc;
     return mips_filter_ignore((const float*)ix->out_s.p, (const int64_t*)ix->out_i.p, ignore_device, nq, k_fetch, k, out_scores_device,
                               out_idx_device, ix->device, hip_stream);
+}
+
+int mips_search_fused(mips_index_t* ix, const void* q_device, int q_dtype, int64_t nq, int k, int normalize, const int64_t* ignore_device,
+                      float* out_scores_device, int64_t* out_idx_device, int64_t idx_offset, void* hip_stream) {
+    return search_fused_impl("mips_search_fused", ix, q_device, q_dtype, nq, k, normalize, ignore_device, out_scores_device, out_idx_device, idx_offset,
+                             nullptr, 0, 0, hip_stream);
+}
+
+int mips_search_fused_grp(mips_index_t* ix, const void* q_device, int q_dtype, int64_t nq, int k, int normalize, const int64_t* ignore_device,
+                          float* out_scores_device, int64_t* out_idx_device, int64_t idx_offset, const int32_t* q_labels, int grp_mode, int flags,
+                          void* hip_stream) {
+    return search_fused_impl(q_labels ? "mips_search_fused_grp" : "mips_search_fused", ix, q_device, q_dtype, nq, k, normalize, ignore_device,
+                             out_scores_device, out_idx_device, idx_offset, q_labels, grp_mode, flags, hip_stream);
 }
 
 int mips_merge_topk(const float* cand_s, const int64_t* cand_i, int64_t nq, int parts, int k, int metric, float* out_s,

@@ -75,7 +75,19 @@ struct ResolveArgs {
     const double* xmax2 = nullptr; // max_i |x_i|^2
     const double* dres2 = nullptr; // max_i |x_i - bf16 x_i|^2 (fp32-exact index)
     double err_c = 0.0;            // MFMA accumulation: |approximate - exact product sum| <= err_c |q| max|x|
+    // the search that flagged was a grouped one (mips_search_fused_grp): a row becomes a hit of query q only if the group rule
+    // admits it -- otherwise the settlement would bring back what the scan left out.  nullptr: no rule (tested like `ignore`)
+    const int* rlab = nullptr;     // one label per row
+    const int* qlab = nullptr;     // [nq] one label per query
+    int grp_only = 0;              // 1 = only mode, 0 = exclude mode
 };
+
+// (the rule itself: scan_kernel_wide.hpp, which includes this header)
+__device__ __forceinline__ bool group_admits(int lab, int ql, int only);
+// may row `row` become a hit of query `qid`?
+__device__ __forceinline__ bool resolve_admits(const ResolveArgs& a, int64_t row, int qid) {
+    return a.qlab == nullptr || group_admits(a.rlab[row], a.qlab[qid], a.grp_only);
+}
 
 template <bool L2>
 __device__ __forceinline__ float resolve_key(double dot, double qq, double phi) {
@@ -172,7 +184,7 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void exact_filter_kernel(Resolv
             if (row < a.ntotal) {
 #pragma unroll
                 for (int j = 0; j < RESOLVE_QB; ++j) {
-                    if (j0 + j < n && resolve_key<L2>(acc[j], qn[j], a.phi) >= kk[j]) {
+                    if (j0 + j < n && resolve_key<L2>(acc[j], qn[j], a.phi) >= kk[j] && resolve_admits(a, row, a.ids[j0 + j])) {
                         const int pos = atomicAdd(&a.hit_n[j0 + j], 1);
                         if (pos < RESOLVE_CAP) {
                             a.hit_d[(size_t)(j0 + j) * RESOLVE_CAP + pos] = acc[j];
@@ -328,6 +340,7 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void exact_filter_mfma_kernel(R
                     const int64_t crow = tile * 16 + 4 * (int64_t)(l >> 4) + r;
                     const int cj = l & 15;
                     const int qid = qid_s[cj];
+                    if (!resolve_admits(a, crow, qid)) continue; // (uniform: every lane reads the same pair)
                     double dot = 0.0;
                     for (int c0 = 0; c0 < nchunk; c0 += 64) { // 64 chunks per round: products to LDS, lane 0 adds them in column order
                         const int cc = c0 + (int)ln;
@@ -483,7 +496,9 @@ __global__ __launch_bounds__(64 * RESOLVE_WAVES) void resolve_overflow_kernel(Re
             const float key = resolve_key<L2>(acc[j], qn[j], a.phi);
             const float wk = __shfl(lk[j], K - 1);
             const int wi = __shfl(li[j], K - 1);
-            unsigned long long m = __ballot(row < a.ntotal && key >= kk[j] && (cnt[j] < K || ranks_before(key, (int)row, wk, wi)));
+            bool in = row < a.ntotal && key >= kk[j] && (cnt[j] < K || ranks_before(key, (int)row, wk, wi));
+            if (in && a.qlab != nullptr) in = ((ovf >> j) & 1u) != 0u && resolve_admits(a, row, a.ids[j0 + j]); // (only an overflowing slot has a query)
+            unsigned long long m = __ballot(in);
             while (m != 0ull) { // one candidate at a time, in row order, the whole wave on it
                 const int l = __ffsll((long long)m) - 1;
                 m &= m - 1ull;

@@ -33,6 +33,7 @@
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v4.hpp"
+#include "scan_kernel_wide.hpp" // (group_admits, LABEL_NONE)
 
 namespace mips {
 
@@ -69,6 +70,10 @@ struct TinyArgs {
     void* q_out;           // [nq][ld] bf16 (pitch ld) or, F32, [nq][plane] float32
     MergeArgs m;           // part_s / part_i / ncand / ll / docs / ld / k / metric / phi / idx_offset / margin fields;
                            // qbuf, out_s, out_i are set by the kernel (LDS)
+    // hook_grouped_kernel (GRP): the group rule of mips_search_wide_grp (scan_kernel_wide.hpp, group_admits) in the scan
+    const int* rlab;       // one label per row, allocated in whole 128-row tiles (16-byte aligned: a lane's four rows are one load)
+    const int* qlab;       // [nq] one label per query (device); LABEL_NONE = not filtered
+    int grp_only;          // 1 = only the rows of the query's group answer, 0 = every row but those
 };
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -367,8 +372,14 @@ __device__ __forceinline__ double tiny_seq_dot_f32(const float* x, const float* 
     return acc;
 }
 
-template <bool L2, bool F32>
-__global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a) {
+// The body of both kernels below.  GRP: lane (c, g) also holds the label of query c and loads the labels of its four rows of a
+// tile -- ONE aligned 16-byte load, issued with the tile's row loads and in flight under the MFMAs; a row the group rule does
+// not admit scores -inf BEFORE the insert test.  It is never inserted, hence never "dropped from a full list": lb / gbnd / bnd
+// bound the admitted rows outside the pool, which is all the certificate of an admitted pool needs (max |x|^2 over ALL rows is
+// the larger, conservative number).  Phase 2 is the same code; the exact pass of flagged queries applies the rule again
+// (ResolveArgs::rlab / qlab, set by the host from the same pointers).
+template <bool L2, bool F32, bool GRP>
+__device__ __forceinline__ void tiny_search_body(const TinyArgs& a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* qs = reinterpret_cast<uint16_t*>(smem);                            // [16][ld] staged queries
     float* wl_s = reinterpret_cast<float*>(smem + 16 * a.ld * 2);                // [16][TINY_WL] this workgroup's lane lists
@@ -400,6 +411,8 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
     const int ks128 = a.ld / 128; // 1 .. 8 groups of four 32-k steps
     const int gw = blockIdx.x * TINY_WAVES + wave;
     bf16x8 av[32];
+    i32x4 lab4 = {0, 0, 0, 0}; // GRP: the labels of rows 16 tile + 4 g .. + 3
+    int ql = LABEL_NONE;       // GRP: the label of query c
     {
         const int t0 = gw < a.ntiles ? gw : a.ntiles - 1; // (idle waves load a valid tile and drop it)
         const uint16_t* arow = a.docs + ((size_t)t0 * 16 + c) * a.ld + 8 * g;
@@ -409,6 +422,10 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
 #pragma unroll
                 for (int u = 4 * u4; u < 4 * u4 + 4; ++u) av[u] = *reinterpret_cast<const bf16x8*>(arow + 32 * u);
             }
+        if constexpr (GRP) {
+            lab4 = *reinterpret_cast<const i32x4*>(a.rlab + (size_t)t0 * 16 + 4 * g);
+            ql = a.qlab[c < a.nq ? c : 0];
+        }
     }
     double xm = 0.0, xres = 0.0;
     if (tid == 0 && a.m.nflag != nullptr) {
@@ -491,6 +508,7 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
 #pragma unroll
                     for (int u = 4 * u4; u < 4 * u4 + 4; ++u) av[u] = *reinterpret_cast<const bf16x8*>(arow + 32 * u);
                 }
+            if constexpr (GRP) lab4 = *reinterpret_cast<const i32x4*>(a.rlab + (size_t)tile * 16 + 4 * g);
         }
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -505,7 +523,8 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
         const int base = tile * 16 + 4 * g;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float sc = (int64_t)(base + r) < a.ntotal ? acc[r] : -INFINITY;
+            float sc = (int64_t)(base + r) < a.ntotal ? acc[r] : -INFINITY;
+            if constexpr (GRP) sc = group_admits(lab4[r], ql, a.grp_only) ? sc : -INFINITY;
             if (sc > ls[TINY_KL - 1]) list_insert<TINY_KL>(ls, li, sc, base + r);
         }
     }
@@ -830,6 +849,17 @@ __global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a
             ++w;
         }
     }
+}
+
+template <bool L2, bool F32>
+__global__ __launch_bounds__(TINY_THREADS, 1) void tiny_search_kernel(TinyArgs a) {
+    tiny_search_body<L2, F32, false>(a);
+}
+
+// mips_search_fused_grp: the same launch under the group rule (a.rlab, a.qlab, a.grp_only)
+template <bool L2, bool F32>
+__global__ __launch_bounds__(TINY_THREADS, 1) void hook_grouped_kernel(TinyArgs a) {
+    tiny_search_body<L2, F32, true>(a);
 }
 
 } // namespace mips

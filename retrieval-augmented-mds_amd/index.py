@@ -665,17 +665,26 @@ class MipsIndex:
         del keep, sel_keep, grp_keep
         return out
 
-    def search_fused(self, x, k: int, normalize: bool = False, ignore=None, idx_offset: int = 0):
+    def search_fused(self, x, k: int, normalize: bool = False, ignore=None, idx_offset: int = 0, groups=None, group_mode: str = "exclude"):
         """The scoring hook's search in one call on CUDA tensors (include/mips_hip.h, mips_search_fused): optional
         row normalisation of float32 queries (the caller's tensor is not modified), top-k, and the ignore filter of
         sotasum/mips.py:388-398 (`ignore`: int64 ids, one per query).  One kernel launch for <= 16 queries on a small
-        index; nothing synchronises."""
+        index; nothing synchronises.
+        groups (an int array [nq], NumPy -> host, CUDA tensor -> device) with group_mode: the group rule of search_wide, applied
+        in the same one launch (include/mips_hip_hook.h, mips_search_fused_grp); `ignore` applies on top of it.  bf16 and f32
+        indexes of at most 1024 columns, as search_wide."""
         import torch
 
         k = int(k)
+        if groups is not None:  # (the storages and widths the grouped wide search serves)
+            if self._f8:
+                raise NotImplementedError("search_fused(groups=) serves 'bf16' and 'f32' indexes, not e4m3 storage")
+            if self._d > 1024:
+                raise NotImplementedError("search_fused(groups=) serves rows of at most 1024 columns")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         if not is_dev:
             raise ValueError("search_fused needs a CUDA tensor")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self._grp_args(groups, group_mode, nq, "search_fused")
         dev = f"cuda:{self.device}"
         ig = None
         if ignore is not None:
@@ -685,10 +694,16 @@ class MipsIndex:
         D = torch.empty((nq, k), dtype=torch.float32, device=dev)
         I = torch.empty((nq, k), dtype=torch.int64, device=dev)
         with self._mutex:
-            _lib.check(self._lib.mips_search_fused(self._h, ptr, code, nq, k, int(bool(normalize)),
-                                                   ig.data_ptr() if ig is not None else None, D.data_ptr(), I.data_ptr(),
-                                                   int(idx_offset), _stream_handle(self.device)), "mips_search_fused")
-        del keep, ig
+            if groups is not None:
+                _lib.check(self._lib.mips_search_fused_grp(self._h, ptr, code, nq, k, int(bool(normalize)),
+                                                           ig.data_ptr() if ig is not None else None, D.data_ptr(), I.data_ptr(),
+                                                           int(idx_offset), grp_ptr, grp_mode, grp_flag, _stream_handle(self.device)),
+                           "mips_search_fused_grp")
+            else:
+                _lib.check(self._lib.mips_search_fused(self._h, ptr, code, nq, k, int(bool(normalize)),
+                                                       ig.data_ptr() if ig is not None else None, D.data_ptr(), I.data_ptr(),
+                                                       int(idx_offset), _stream_handle(self.device)), "mips_search_fused")
+        del keep, ig, grp_keep
         return D, I
 
     def search_packed(self, x, k: int, idx_offset: int = 0, tail_stream=None):

@@ -706,7 +706,8 @@ class Mips:
             scores, indices = out_s, out_i
         return scores, indices
 
-    def search_device(self, queries, ignore_indexes=None, k: int = 10, prepare: bool = True, return_rows: bool = False):
+    def search_device(self, queries, ignore_indexes=None, k: int = 10, prepare: bool = True, return_rows: bool = False,
+                      ignore_groups=None):
         """Device-resident form of `_prepare_query` + `search`: takes the query CLS
         vectors as a CUDA tensor [B, d] straight from the encoder -- removing the
         `.detach().cpu().float().numpy()` hop of retriever_generator.py:143 -- normalises them on the
@@ -714,13 +715,16 @@ class Mips:
         mips.py:388-398 on the device and returns CUDA (scores [B, k], indices [B, k]); nothing
         synchronises.  return_rows=True: (scores, indices, rows [B, k, d] float32 CUDA), the stored rows of the hits gathered
         on the device, still without a synchronisation (NaN rows at -1 slots) -- with a frozen document encoder they are the
-        `mips_cls` of retriever_generator.py:158-172 and go straight into cosine_rescore."""
-        out = self._search_device(queries, ignore_indexes, k, prepare)
+        `mips_cls` of retriever_generator.py:158-172 and go straight into cosine_rescore.
+        ignore_groups (per-query values of index_column, e.g. the queries' `aid`): the group filter of search(), in the same
+        one launch on a MipsIndex (search_fused(groups=)); the groups are set on first use and both filters combine.  A sharded
+        index serves it through search_wide(groups=) cut to k."""
+        out = self._search_device(queries, ignore_indexes, k, prepare, ignore_groups)
         if not return_rows:
             return out
         return out[0], out[1], self._index().reconstruct_batch(out[1])
 
-    def _search_device(self, queries, ignore_indexes, k: int, prepare: bool):
+    def _search_device(self, queries, ignore_indexes, k: int, prepare: bool, ignore_groups=None):
         import torch
 
         from .index import filter_ignore
@@ -730,6 +734,11 @@ class Mips:
         if not (isinstance(q, torch.Tensor) and q.is_cuda):
             raise ValueError("search_device expects a CUDA tensor [B, d]")
         want_norm = bool(prepare and self.normalize and self.metric_type == METRIC_INNER_PRODUCT)
+        groups = None
+        if ignore_groups is not None:
+            if self.index_name not in self.embeddings._groups:
+                self.embeddings.set_groups(self.index_name, self.index_column)
+            groups = self.embeddings.group_codes(self.index_name, ignore_groups, "exclude")
         if isinstance(index, MipsIndex):
             # prepare + search + ignore filter in one library call: one kernel launch at the reference's own sizes
             # (B <= 16 queries, ~10^4 documents), the same separate steps otherwise -- identical results
@@ -738,11 +747,19 @@ class Mips:
                 qq = qq[:, :-1]  # augment_xq's zero column (not checked here: that would synchronise)
             if want_norm:
                 qq = qq.float()
+            if groups is not None:
+                return index.search_fused(qq.contiguous(), k, normalize=want_norm, ignore=ignore_indexes, groups=groups, group_mode="exclude")
             return index.search_fused(qq.contiguous(), k, normalize=want_norm, ignore=ignore_indexes)
         if want_norm:
             q = l2_normalize_(q.detach().float().contiguous().clone())
         if q.dim() == 2 and self.metric_type == METRIC_L2 and q.shape[1] == index.d + 1:
             q = q[:, :-1].contiguous()  # augment_xq's zero column (not checked here: that would synchronise)
+        if groups is not None:  # a sharded index: the wide search under the rule, cut to k
+            if ignore_indexes is None:
+                s, i = index.search_wide(q, k, groups=groups, group_mode="exclude")
+                return s[:, :k], i[:, :k]
+            s, i = index.search_wide(q, k + 1, groups=groups, group_mode="exclude")
+            return filter_ignore(s, i, ignore_indexes, k)
         if ignore_indexes is None:
             return index.search(q, k)
         s, i = index.search(q, k + 1)
