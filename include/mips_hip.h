@@ -48,6 +48,9 @@ extern "C" {
 #define MIPS_DTYPE_FP8_E4M3 2 /* OCP e4m3 bytes: index storage AND queries quantised to e4m3, fp8 MFMA (d <= 1024, k <= 13) */
 #define MIPS_DTYPE_FP8_E4M3_DOCS 3 /* index storage only (mips_index_create): OCP e4m3 rows, bf16 QUERIES -- BASELINE config 5 as it is
                                       worded ("fp8 e4m3 doc embeddings"); d <= 1024 */
+#define MIPS_DTYPE_SQ8 4 /* index storage only (mips_index_create): faiss "SQ8" -- one byte per element, 256 uniform levels over each
+                            column's TRAINED range, bf16 queries; inner product only, d <= 1024 (include/mips_hip_sq8.h).  As the
+                            src_dtype of mips_index_add / the out_dtype of mips_index_reconstruct on such an index: raw codes */
 
 /* faiss.METRIC_INNER_PRODUCT / faiss.METRIC_L2 as used by mips.py:306,316,369,371 */
 #define MIPS_METRIC_IP 0
@@ -107,6 +110,8 @@ const char* mips_last_error(void);
  *                        bf16 query precision; the rows are up-converted on their way into the bf16 MFMA
  *                        (csrc/scan_kernel_e8.hpp), which costs vector instructions -- for FEW queries per pass (<= 64 per tile),
  *                        where bytes bind.  Canonical score: exact products of (e4m3 row element, bf16 query element), fp64 sum
+ *   MIPS_DTYPE_SQ8       1 B/element, a trained 8-bit scalar quantiser (mips_hip_sq8.h): train, then add.  Inner product only
+ *                        (MIPS_METRIC_L2: MIPS_E_UNSUPPORTED -- decoded rows have no constant norm, which the L2 rule presumes)
  *   MIPS_DTYPE_F32       fp32-exact: results are those of an fp32 brute force on the caller's values -- what the Python
  *                        facade (Mips / KnowledgeBase.add_faiss_index / inner_product) creates by default, because the
  *                        reference's embeddings are fp32 and "drop-in" means ITS neighbours

@@ -22,10 +22,11 @@ HEADER_SHARDED = os.path.join(_ROOT, "include", "mips_hip_sharded.h")  # helpers
 HEADER_UPDATE = os.path.join(_ROOT, "include", "mips_hip_update.h")  # calls that change the rows an index holds
 HEADER_ROWS = os.path.join(_ROOT, "include", "mips_hip_rows.h")  # stored rows, labels and scores by row id
 HEADER_HOOK = os.path.join(_ROOT, "include", "mips_hip_hook.h")  # the one-launch hook search under a group filter
+HEADER_SQ8 = os.path.join(_ROOT, "include", "mips_hip_sq8.h")  # the trained 8-bit scalar quantiser of an SQ8 index
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
-DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3, DTYPE_FP8_E4M3_DOCS = 0, 1, 2, 3
+DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3, DTYPE_FP8_E4M3_DOCS, DTYPE_SQ8 = 0, 1, 2, 3, 4
 METRIC_IP, METRIC_L2 = 0, 1
 Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP, SEL_DEVICE, GRP_DEVICE = 1, 2, 4, 8, 16, 32
 IDS_DEVICE, ROWS_ZERO_MISSING = 64, 128  # include/mips_hip_rows.h
@@ -42,7 +43,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -153,7 +154,13 @@ def _bind(lib):
     sig_hook = {  # include/mips_hip_hook.h
         "mips_search_fused_grp": (i32, [vp, vp, i32, i64, i32, i32, vp, vp, vp, i64, vp, i32, i32, vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook}.items():
+    sig_sq8 = {  # include/mips_hip_sq8.h
+        "mips_index_sq8_train": (i32, [vp, vp, i64, i32, i32, vp]),
+        "mips_index_sq8_set_params": (i32, [vp, vp, vp]),
+        "mips_index_sq8_get_params": (i32, [vp, vp, vp]),
+        "mips_index_sq8_is_trained": (i32, [vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -176,6 +183,7 @@ EXPORTS_SHARDED = ("mips_range_merge_records",)  # what include/mips_hip_sharded
 EXPORTS_UPDATE = ("mips_index_remove",)  # what include/mips_hip_update.h declares; the same library exports it
 EXPORTS_ROWS = ("mips_index_reconstruct", "mips_index_gather_labels", "mips_score_subset")  # include/mips_hip_rows.h, likewise
 EXPORTS_HOOK = ("mips_search_fused_grp",)  # include/mips_hip_hook.h, likewise
+EXPORTS_SQ8 = ("mips_index_sq8_train", "mips_index_sq8_set_params", "mips_index_sq8_get_params", "mips_index_sq8_is_trained")  # mips_hip_sq8.h
 
 
 def range_record_words(nq: int, stride: int) -> int:

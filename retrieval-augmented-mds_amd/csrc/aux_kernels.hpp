@@ -91,6 +91,23 @@ struct ElemF8 {
 #endif
     }
 };
+// the codes 0 .. 255 of the 8-bit scalar-quantised storage (MIPS_DTYPE_SQ8) as the integers they are.  byte_to_f32: the
+// compiler selects v_cvt_f32_ubyteN for the conversion of a masked byte (there is no builtin for it)
+template <int N>
+__host__ __device__ __forceinline__ float byte_to_f32(unsigned w) { return (float)((w >> (8 * N)) & 0xffu); }
+struct ElemU8 {
+    typedef uint8_t type;
+    static constexpr int PER16 = 16;
+    __device__ static __forceinline__ float get(const u32x4& v, int e) {
+        const unsigned w = v[e >> 2];
+        switch (e & 3) {
+        case 0: return byte_to_f32<0>(w);
+        case 1: return byte_to_f32<1>(w);
+        case 2: return byte_to_f32<2>(w);
+        default: return byte_to_f32<3>(w);
+        }
+    }
+};
 
 // ------------------------------------------------------------------ conversion into [rows][ld] bf16
 // one thread per 8 output elements; columns >= d are written as zero.

@@ -132,6 +132,23 @@ inline const ScanInstance* e8_instances(int* n) {
     MIPS_TABLE_END(t);
 }
 
+// sq8_scan_kernel (8-bit codes x bf16 queries, MIPS_DTYPE_SQ8): scan_kernel_e8's plan and instance set -- same pitches, tiles,
+// pools, ring depths and LDS bytes -- with the conversion step u8 -> bf16
+#define MIPS_SQ8_ROW(LDB, NCB, STG, NT, PUB, PIPE, KW)                                                                             \
+    {LDB, NT, PUB, NCB, 512, e8_lds(LDB, NCB, STG, PIPE, KW), (const void*)mips::sq8_scan_kernel<6, LDB, NCB, STG, NT, PUB, PIPE, KW>, \
+     "mips::sq8_scan_kernel<6, " #LDB ", " #NCB ", " #STG ", " #NT ", " #PUB ", " #PIPE ", " #KW ">", ScanArgKind::E8}
+#define MIPS_SQ8_PITCH(LDB, PUB)                                                                               \
+    MIPS_SQ8_ROW(LDB, 1, 4, true, PUB, true, 8), MIPS_SQ8_ROW(LDB, 2, 4, true, PUB, true, 4),                  \
+    MIPS_SQ8_ROW(LDB, 4, 3, true, PUB, true, 4), MIPS_SQ8_ROW(LDB, 4, 3, false, PUB, true, 4)
+#define MIPS_SQ8_PITCH_1024(PUB)                                                                               \
+    MIPS_SQ8_ROW(1024, 1, 3, true, PUB, true, 8), MIPS_SQ8_ROW(1024, 2, 3, true, PUB, true, 4),                \
+    MIPS_SQ8_ROW(1024, 4, 3, true, PUB, false, 4), MIPS_SQ8_ROW(1024, 4, 3, false, PUB, false, 4)
+#define MIPS_SQ8_POOL(PUB) MIPS_SQ8_PITCH(256, PUB), MIPS_SQ8_PITCH(512, PUB), MIPS_SQ8_PITCH(768, PUB), MIPS_SQ8_PITCH_1024(PUB)
+inline const ScanInstance* sq8_instances(int* n) {
+    static const ScanInstance t[] = {MIPS_SQ8_POOL(1), MIPS_SQ8_POOL(2), MIPS_SQ8_POOL(4)};
+    MIPS_TABLE_END(t);
+}
+
 // generic scan_kernel<K'>: any row pitch (a multiple of 64), the [hi | lo] planes of the fp32-exact index
 template <int KL>
 const ScanInstance* generic_instance() {
@@ -246,9 +263,10 @@ int choose_scan(const mips_index* ix, const SearchCall& c, int64_t nq, ScanPlan&
     // e4m3 documents x bf16 queries (MIPS_DTYPE_FP8_E4M3_DOCS): scan_kernel_e8, tiles of 32 queries (up to 32 queries, and at
     // row pitch 1024) or 64; pools of 8 / 10 / 16 / 32 out of 8 sub-lists of 6 per (query, split), the class words vouching for
     // 8 PUB documents
+    // (MIPS_DTYPE_SQ8: the same plan over 8-bit codes, sq8_scan_kernel)
     const bool e8 = ix->mixed;
     if (e8) {
-        if (c.ld % 256 != 0 || c.ld > 1024) return fail(MIPS_E_UNSUPPORTED, "e4m3-documents index: d must pad to 256/512/768/1024");
+        if (c.ld % 256 != 0 || c.ld > 1024) return fail(MIPS_E_UNSUPPORTED, "one-byte rows x bf16 queries: d must pad to 256/512/768/1024");
         variant = 3;
     } else if (f8) {
         if (c.ld % 256 != 0 || c.ld > 1024 || KL > 16) return fail(MIPS_E_UNSUPPORTED, "fp8 index: d must pad to 256/512/768/1024 and k <= 13");
@@ -295,7 +313,7 @@ int choose_scan(const mips_index* ix, const SearchCall& c, int64_t nq, ScanPlan&
     int nrow = 0;
     const ScanInstance* rows = nullptr;
     if (e8) { // pools of 8 PUB: K' = 8 / 10, 16 / 32
-        rows = e8_instances(&nrow);
+        rows = ix->sq8 ? sq8_instances(&nrow) : e8_instances(&nrow);
         pl.row = find_instance(rows, nrow, c.ld, nt, KL <= 8 ? 1 : KL <= 16 ? 2 : 4, e8_ncb(nq));
     } else if (want_k3) { // pool of 8 PUB candidates: every sub-list vouches for its PUB-th best
         rows = k3_instances(&nrow);
@@ -483,6 +501,7 @@ int launch_tail(mips_index* ix, const SearchCall& c, const ScanPlan& pl, const m
     const int rgrid = (int)((nq + (64 / KL) - 1) / (64 / KL));
     if (f32r && l2) mips::rescore_rank_kernel<KL, mips::ElemF32, true><<<rgrid, 64, 0, st>>>(m, cand, nq);
     else if (f32r) mips::rescore_rank_kernel<KL, mips::ElemF32, false><<<rgrid, 64, 0, st>>>(m, cand, nq);
+    else if (ix->sq8) mips::rescore_rank_kernel<KL, mips::ElemU8, false, mips::ElemBF16><<<rgrid, 64, 0, st>>>(m, cand, nq); // (inner product only)
     else if (e8 && l2) mips::rescore_rank_kernel<KL, mips::ElemF8, true, mips::ElemBF16><<<rgrid, 64, 0, st>>>(m, cand, nq);
     else if (e8) mips::rescore_rank_kernel<KL, mips::ElemF8, false, mips::ElemBF16><<<rgrid, 64, 0, st>>>(m, cand, nq);
     else if (f8 && l2) mips::rescore_rank_kernel<KL, mips::ElemF8, true><<<rgrid, 64, 0, st>>>(m, cand, nq);
@@ -543,5 +562,9 @@ int launch_search(mips_index* ix, const SearchCall& c, int64_t nq, int k, float*
 }
 
 #undef MIPS_TABLE_END
+#undef MIPS_SQ8_ROW
+#undef MIPS_SQ8_PITCH
+#undef MIPS_SQ8_PITCH_1024
+#undef MIPS_SQ8_POOL
 
 } // namespace

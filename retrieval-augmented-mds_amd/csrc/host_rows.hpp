@@ -55,7 +55,7 @@ int index_reconstruct(mips_index* ix, const int64_t* ids, int64_t n, int64_t idx
     a.idx_offset = idx_offset;
     a.out = out;
     a.out_ld = out_ld;
-    a.fill = (flags & MIPS_ROWS_ZERO_MISSING) ? 0u : !raw ? 0x7fc00000u : ix->esize == 2 ? 0x7fc0u : 0x7fu;
+    a.fill = (flags & MIPS_ROWS_ZERO_MISSING) ? 0u : !raw ? 0x7fc00000u : ix->esize == 2 ? 0x7fc0u : ix->sq8 ? 0u : 0x7fu; // (SQ8 has no NaN code)
     if (!out_dev) { // compute into a packed device buffer; only columns 0 .. d - 1 of the caller's rows are written
         rc = ix->row_out.ensure((size_t)n * ix->d * osize);
         if (rc) return rc;
@@ -66,7 +66,13 @@ int index_reconstruct(mips_index* ix, const int64_t* ids, int64_t n, int64_t idx
     if (f32x) mips::rows_gather_kernel<mips::ElemF32, false><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
     else if (ix->esize == 2 && raw) mips::rows_gather_kernel<mips::ElemBF16, true><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
     else if (ix->esize == 2) mips::rows_gather_kernel<mips::ElemBF16, false><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
-    else if (raw) mips::rows_gather_kernel<mips::ElemF8, true><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
+    else if (ix->sq8 && raw) mips::rows_gather_kernel<mips::ElemU8, true><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
+    else if (ix->sq8) { // the codes as float32, decoded in place behind the gather (rows of "no row" keep their fill)
+        mips::rows_gather_kernel<mips::ElemU8, false><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
+        if (ix->sq8_trained) // (an untrained index holds no row: every id is "no row" and keeps its fill)
+            mips::sq8_decode_rows_kernel<<<grid_for(n * ix->d, 256), 256, 0, st>>>((float*)a.out, a.out_ld, d_ids, n, (int)ix->d, idx_offset, ix->ntotal,
+                                                                            ix->sq8_params, ix->ld);
+    } else if (raw) mips::rows_gather_kernel<mips::ElemF8, true><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
     else mips::rows_gather_kernel<mips::ElemF8, false><<<grid, mips::ROWS_THREADS, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     if (!out_dev)
@@ -126,7 +132,11 @@ int index_score_subset(mips_index* ix, const void* q, int q_dtype, int64_t nq, c
         if (rc) return rc;
         rc = convert_into(ix, q, nq, q_dtype, q_dev, (uint8_t*)ix->cur.qbuf.p, st, (float*)ix->cur.qf32.p);
     } else {
-        rc = convert_into(ix, q, nq, q_dtype, q_dev, (uint8_t*)ix->cur.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize);
+        if (ix->sq8) {
+            rc = ix->cur.qbias.ensure((size_t)nq * sizeof(double));
+            if (rc) return rc;
+        }
+        rc = convert_into(ix, q, nq, q_dtype, q_dev, (uint8_t*)ix->cur.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize, (double*)ix->cur.qbias.p);
     }
     if (rc) return rc;
     const int64_t* d_ids;
@@ -151,7 +161,10 @@ int index_score_subset(mips_index* ix, const void* q, int q_dtype, int64_t nq, c
     const int grid = rows_grid(npairs, mips::ROWS_THREADS);
     auto go = [&](auto kern) { kern<<<grid, mips::ROWS_THREADS, 0, st>>>(a); };
     if (f32x) l2 ? go(mips::rows_score_kernel<mips::ElemF32, true>) : go(mips::rows_score_kernel<mips::ElemF32, false>);
-    else if (ix->mixed) l2 ? go(mips::rows_score_kernel<mips::ElemF8, true, mips::ElemBF16>) : go(mips::rows_score_kernel<mips::ElemF8, false, mips::ElemBF16>);
+    else if (ix->sq8) { // S on the codes and q', then D = S + B_q as the searches report it
+        go(mips::rows_score_kernel<mips::ElemU8, false, mips::ElemBF16>);
+        mips::sq8_bias_kernel<<<grid_for(npairs, 256), 256, 0, st>>>(a.out, nullptr, (const double*)ix->cur.qbias.p, nq, k);
+    } else if (ix->mixed) l2 ? go(mips::rows_score_kernel<mips::ElemF8, true, mips::ElemBF16>) : go(mips::rows_score_kernel<mips::ElemF8, false, mips::ElemBF16>);
     else if (ix->esize == 1) l2 ? go(mips::rows_score_kernel<mips::ElemF8, true>) : go(mips::rows_score_kernel<mips::ElemF8, false>);
     else l2 ? go(mips::rows_score_kernel<mips::ElemBF16, true>) : go(mips::rows_score_kernel<mips::ElemBF16, false>);
     HIP_TRY(hipGetLastError());

@@ -264,6 +264,7 @@ int resolve_flagged(mips_index* ix, const SearchCall& c, SearchReport& rep, int6
         if (f32x) rc = l2 ? go(mips::exact_filter_mfma_kernel<true, true>) : go(mips::exact_filter_mfma_kernel<false, true>);
         else rc = l2 ? go(mips::exact_filter_mfma_kernel<true, false>) : go(mips::exact_filter_mfma_kernel<false, false>);
     } else if (f32x) rc = l2 ? go(mips::exact_filter_kernel<mips::ElemF32, true>) : go(mips::exact_filter_kernel<mips::ElemF32, false>);
+    else if (ix->sq8) rc = go(mips::exact_filter_kernel<mips::ElemU8, false, mips::ElemBF16>);
     else if (ix->mixed) rc = l2 ? go(mips::exact_filter_kernel<mips::ElemF8, true, mips::ElemBF16>) : go(mips::exact_filter_kernel<mips::ElemF8, false, mips::ElemBF16>);
     else if (ix->esize == 1) rc = l2 ? go(mips::exact_filter_kernel<mips::ElemF8, true>) : go(mips::exact_filter_kernel<mips::ElemF8, false>);
     else rc = l2 ? go(mips::exact_filter_kernel<mips::ElemBF16, true>) : go(mips::exact_filter_kernel<mips::ElemBF16, false>);
@@ -278,6 +279,7 @@ int resolve_flagged(mips_index* ix, const SearchCall& c, SearchReport& rep, int6
     lds = mips::RESOLVE_QB * a.ld * (int)sizeof(double) + mips::RESOLVE_WAVES * 64 * 9 * 16; // (the plain pass's layout; the lists
                                                                                             // meet over the tiles)
     if (f32x) rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemF32, true>) : go(mips::resolve_overflow_kernel<mips::ElemF32, false>);
+    else if (ix->sq8) rc = go(mips::resolve_overflow_kernel<mips::ElemU8, false, mips::ElemBF16>);
     else if (ix->mixed) rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemF8, true, mips::ElemBF16>) : go(mips::resolve_overflow_kernel<mips::ElemF8, false, mips::ElemBF16>);
     else if (ix->esize == 1) rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemF8, true>) : go(mips::resolve_overflow_kernel<mips::ElemF8, false>);
     else rc = l2 ? go(mips::resolve_overflow_kernel<mips::ElemBF16, true>) : go(mips::resolve_overflow_kernel<mips::ElemBF16, false>);

@@ -105,6 +105,7 @@ struct Buffer {
 // event its tail records and whether a tail may still be reading it.
 struct ScratchSet {
     Buffer qbuf, qf32, gthr, part_s, part_i, cand, mbnd, mflag;
+    Buffer qbias; // SQ8 index: B_q of the staged queries, one double each (SearchCall::qbias)
     Event tail_done;
     bool tail_pending = false;
 };
@@ -123,6 +124,12 @@ struct mips_index {
     int esize = 2; // bytes per stored element
     int qsize = 2; // bytes per STAGED query element: esize, except MIPS_DTYPE_FP8_E4M3_DOCS (e4m3 rows, bf16 queries: `mixed`)
     bool mixed = false;
+    // 8-bit scalar-quantised storage (MIPS_DTYPE_SQ8; host_sq8.hpp).  `mixed` holds as well: one-byte rows, bf16 staged queries.
+    // sq8_params = [vmin | vdiff | s | o], ld floats each (columns >= d zero): what encode, query staging and decode read
+    bool sq8 = false;
+    bool sq8_trained = false;
+    DeviceArray<float> sq8_params;
+    Buffer sq8_part; // training: the row parts' minima / maxima / flags, and the candidate parameters
     int doc_dtype = MIPS_DTYPE_BF16;
     int metric = MIPS_METRIC_IP;
     int64_t ntotal = 0;
@@ -235,6 +242,7 @@ struct SearchCall {
     bool timed = true;             // the scan may record its event pair and names itself in last_kernel (a nested launch: no)
     int metric = MIPS_METRIC_IP;   // index metric unless MIPS_FORCE_IP
     int margin = 0;                // margin_mode() of this call
+    const double* qbias = nullptr; // SQ8 index: B_q per staged query, added where the call's final scores stand (sq8_finish)
 };
 
 namespace {
@@ -342,7 +350,7 @@ int grow(mips_index* ix, int64_t need_rows, hipStream_t st, bool exact = false) 
 // out_esize: bytes per OUTPUT element (0 = the index storage's; query staging passes ix->qsize)
 int convert_into(mips_index* ix, const void* src, int64_t n, int src_dtype, int src_is_device, uint8_t* dst,
                  hipStream_t st, float* keep_f32 = nullptr, int64_t pad_rows = 0, uint32_t* zero = nullptr,
-                 int64_t zero_words = 0, int out_esize = 0) {
+                 int64_t zero_words = 0, int out_esize = 0, double* sq8_bias = nullptr) {
     const int d = (int)ix->d, ld = ix->ld;
     if (out_esize == 0) out_esize = ix->esize;
     const size_t esz = src_dtype == MIPS_DTYPE_F32 ? 4 : src_dtype == MIPS_DTYPE_BF16 ? 2 : 1;
@@ -366,11 +374,29 @@ int convert_into(mips_index* ix, const void* src, int64_t n, int src_dtype, int 
             else
                 mips::split_rows_kernel<uint16_t><<<grid_for(items, 256), 256, 0, st>>>((const uint16_t*)s, nr, d, d, (uint16_t*)out, ix->plane, keep);
         } else {
+            // (both SQ8 branches below read the trained parameters on the device: no launch without them, whoever calls)
+            if (ix->sq8 && !ix->sq8_trained) return fail(MIPS_E_INVALID, "the SQ8 index is not trained (mips_index_sq8_train)");
             const bool last = r0 + nr == n;
             const int64_t n_out = nr + (last ? pad_rows : 0);
             uint32_t* z = last ? zero : nullptr;
             const int64_t zw = last ? zero_words : 0;
-            if (out_esize == 2) {
+            if (ix->sq8 && out_esize == 2) { // query staging of an SQ8 index: q' = bf16(q s), B_q (chunks: the launch of the last
+                const int64_t items = n_out * (ld / 8); // one pads and clears; every launch writes its own queries' B_q)
+                if (src_dtype != MIPS_DTYPE_F32 && src_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "SQ8 index: queries are float32 or bf16");
+                uint16_t* qo = (uint16_t*)out;
+                if (src_dtype == MIPS_DTYPE_F32)
+                    mips::sq8_stage_queries_kernel<float><<<grid_for(items, 256), 256, 0, st>>>((const float*)s, nr, d, ix->sq8_params, qo, ld, n_out, z, zw, sq8_bias + r0);
+                else
+                    mips::sq8_stage_queries_kernel<uint16_t><<<grid_for(items, 256), 256, 0, st>>>((const uint16_t*)s, nr, d, ix->sq8_params, qo, ld, n_out, z, zw, sq8_bias + r0);
+            } else if (ix->sq8) { // rows of an SQ8 index: encode (or copy raw codes)
+                const int64_t items = nr * (ld / 16);
+                if (src_dtype == MIPS_DTYPE_F32)
+                    mips::sq8_encode_rows_kernel<float><<<grid_for(items, 256), 256, 0, st>>>((const float*)s, nr, d, ix->sq8_params, out, ld);
+                else if (src_dtype == MIPS_DTYPE_BF16)
+                    mips::sq8_encode_rows_kernel<uint16_t><<<grid_for(items, 256), 256, 0, st>>>((const uint16_t*)s, nr, d, ix->sq8_params, out, ld);
+                else
+                    mips::sq8_encode_rows_kernel<uint8_t><<<grid_for(items, 256), 256, 0, st>>>((const uint8_t*)s, nr, d, ix->sq8_params, out, ld);
+            } else if (out_esize == 2) {
                 const int64_t items = n_out * (ld / 8);
                 if (src_dtype == MIPS_DTYPE_FP8_E4M3) return fail(MIPS_E_INVALID, "e4m3 bytes cannot be staged as bf16 rows");
                 if (src_dtype == MIPS_DTYPE_F32)
@@ -395,8 +421,8 @@ int convert_into(mips_index* ix, const void* src, int64_t n, int src_dtype, int 
 
 // for_query: queries of an e4m3-documents / bf16-queries index are float32 or bf16 (raw e4m3 bytes are rows only)
 bool src_dtype_ok(const mips_index* ix, int t, bool for_query = false) {
-    return t == MIPS_DTYPE_F32 || t == MIPS_DTYPE_BF16 ||
-           (t == MIPS_DTYPE_FP8_E4M3 && ix->esize == 1 && ix->plane == 0 && !(for_query && ix->mixed));
+    return t == MIPS_DTYPE_F32 || t == MIPS_DTYPE_BF16 || (t == MIPS_DTYPE_SQ8 && ix->sq8 && !for_query) || // (raw codes: rows only)
+           (t == MIPS_DTYPE_FP8_E4M3 && ix->esize == 1 && ix->plane == 0 && !ix->sq8 && !(for_query && ix->mixed));
 }
 
 int compute_phi(mips_index* ix, hipStream_t st) {
@@ -412,6 +438,9 @@ int compute_phi(mips_index* ix, hipStream_t st) {
         else if (ix->esize == 2)
             mips::row_sumsq_max_kernel<mips::ElemBF16><<<grid, 256, 0, st>>>((const uint16_t*)ix->rows.p, ix->ntotal, ix->ld,
                                                                               (unsigned long long*)ix->scalar.p);
+        else if (ix->sq8)
+            mips::row_sumsq_max_kernel<mips::ElemU8><<<grid, 256, 0, st>>>(ix->rows, ix->ntotal, ix->ld,
+                                                                            (unsigned long long*)ix->scalar.p);
         else
             mips::row_sumsq_max_kernel<mips::ElemF8><<<grid, 256, 0, st>>>(ix->rows, ix->ntotal, ix->ld,
                                                                             (unsigned long long*)ix->scalar.p);
@@ -435,6 +464,7 @@ int ensure_xmax2(mips_index* ix, hipStream_t st) {
         unsigned long long* out = (unsigned long long*)ix->xmax2_dev.p;
         if (ix->plane > 0) mips::row_sumsq_max_kernel<mips::ElemF32><<<grid, 256, 0, st>>>(ix->rows_f32, ix->ntotal, ix->plane, out);
         else if (ix->esize == 2) mips::row_sumsq_max_kernel<mips::ElemBF16><<<grid, 256, 0, st>>>((const uint16_t*)ix->rows.p, ix->ntotal, ix->ld, out);
+        else if (ix->sq8) mips::row_sumsq_max_kernel<mips::ElemU8><<<grid, 256, 0, st>>>(ix->rows, ix->ntotal, ix->ld, out); // (the norm of the codes)
         else mips::row_sumsq_max_kernel<mips::ElemF8><<<grid, 256, 0, st>>>(ix->rows, ix->ntotal, ix->ld, out);
         HIP_TRY(hipGetLastError());
     }

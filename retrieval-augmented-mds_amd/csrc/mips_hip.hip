@@ -21,6 +21,7 @@
 #include "../../include/mips_hip_update.h"
 #include "../../include/mips_hip_rows.h"
 #include "../../include/mips_hip_hook.h"
+#include "../../include/mips_hip_sq8.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -37,9 +38,12 @@
 #include "select_kernels.hpp"
 #include "remove_kernels.hpp"
 #include "rows_kernels.hpp"
+#include "sq8_kernels.hpp"
+#include "sq8_scan_kernel.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"
+#include "host_sq8.hpp"
 #include "host_launch.hpp"
 #include "host_search.hpp"
 #include "host_wide.hpp"
@@ -61,11 +65,16 @@ int mips_index_create(mips_index_t** out, int device, int64_t d, int doc_dtype, 
     if (d <= 0 || d > (1 << 20)) return fail(MIPS_E_INVALID, "mips_index_create: bad dimension %lld", (long long)d);
     if (metric != MIPS_METRIC_IP && metric != MIPS_METRIC_L2)
         return fail(MIPS_E_INVALID, "mips_index_create: metric must be 0 (inner product) or 1 (L2), got %d", metric);
-    if (doc_dtype != MIPS_DTYPE_BF16 && doc_dtype != MIPS_DTYPE_FP8_E4M3 && doc_dtype != MIPS_DTYPE_F32 && doc_dtype != MIPS_DTYPE_FP8_E4M3_DOCS)
-        return fail(MIPS_E_INVALID, "mips_index_create: index storage dtype must be BF16, FP8_E4M3, FP8_E4M3_DOCS or F32, got %d", doc_dtype);
-    const bool f8_storage = doc_dtype == MIPS_DTYPE_FP8_E4M3 || doc_dtype == MIPS_DTYPE_FP8_E4M3_DOCS;
+    const bool sq8 = doc_dtype == MIPS_DTYPE_SQ8;
+    if (doc_dtype != MIPS_DTYPE_BF16 && doc_dtype != MIPS_DTYPE_FP8_E4M3 && doc_dtype != MIPS_DTYPE_F32 && doc_dtype != MIPS_DTYPE_FP8_E4M3_DOCS && !sq8)
+        return fail(MIPS_E_INVALID, "mips_index_create: index storage dtype must be BF16, FP8_E4M3, FP8_E4M3_DOCS, SQ8 or F32, got %d", doc_dtype);
+    // (one-byte storages share row pitch, element size and the d limit; SQ8 is "e4m3 documents" with another element decode)
+    const bool f8_storage = doc_dtype == MIPS_DTYPE_FP8_E4M3 || doc_dtype == MIPS_DTYPE_FP8_E4M3_DOCS || sq8;
     if (f8_storage && d > 1024)
-        return fail(MIPS_E_UNSUPPORTED, "mips_index_create: fp8 e4m3 storage supports d <= 1024 in this build");
+        return fail(MIPS_E_UNSUPPORTED, "mips_index_create: one-byte storage (fp8 e4m3, SQ8) supports d <= 1024 in this build");
+    if (sq8 && metric != MIPS_METRIC_IP)
+        return fail(MIPS_E_UNSUPPORTED, "mips_index_create: an SQ8 index ranks by inner product only (the L2 rule |q|^2 + phi - 2 q.x presumes rows of "
+                                        "constant norm, which decoded SQ8 rows are not)");
     int count = 0;
     HIP_TRY(hipGetDeviceCount(&count));
     if (device < 0 || device >= count) return fail(MIPS_E_INVALID, "mips_index_create: no HIP device %d (have %d)", device, count);
@@ -77,7 +86,8 @@ int mips_index_create(mips_index_t** out, int device, int64_t d, int doc_dtype, 
     ix->device = device;
     ix->d = d;
     ix->esize = f8_storage ? 1 : 2;
-    ix->mixed = doc_dtype == MIPS_DTYPE_FP8_E4M3_DOCS;
+    ix->sq8 = sq8;
+    ix->mixed = doc_dtype == MIPS_DTYPE_FP8_E4M3_DOCS || sq8;
     ix->qsize = ix->mixed ? 2 : ix->esize;
     // Row pitch.  bf16: the query-stationary kernels exist for pitches of 128 .. 768 (multiples of 128) and
     // 1024, so every d <= 1024 is padded to one of those (zero columns); beyond that the generic kernel
@@ -128,7 +138,8 @@ int mips_index_add(mips_index_t* ix, const void* rows, int64_t n, int src_dtype,
     if (!ix) return fail(MIPS_E_INVALID, "mips_index_add: index is NULL");
     if (n < 0 || (n > 0 && !rows)) return fail(MIPS_E_INVALID, "mips_index_add: bad rows / n");
     if (!src_dtype_ok(ix, src_dtype))
-        return fail(MIPS_E_INVALID, "mips_index_add: src_dtype must be F32 or BF16 (or FP8_E4M3 bytes for an fp8 index)");
+        return fail(MIPS_E_INVALID, "mips_index_add: src_dtype must be F32 or BF16 (or FP8_E4M3 bytes for an fp8 index, SQ8 codes for an SQ8 index)");
+    if (ix->sq8 && !ix->sq8_trained) return fail(MIPS_E_INVALID, "mips_index_add: the SQ8 index is not trained (mips_index_sq8_train)");
     if (n == 0) return MIPS_OK;
     if (ix->ntotal + n > (int64_t)0x7fffff00) return fail(MIPS_E_UNSUPPORTED, "mips_index_add: more than 2^31 rows on one GPU");
     DeviceGuard g(ix->device);
@@ -246,6 +257,7 @@ int mips_index_read_rows(mips_index_t* ix, int64_t row0, int64_t n, void* out_ho
 int mips_index_add_synthetic(mips_index_t* ix, int64_t n, int64_t row0, uint64_t seed, int kind, void* hip_stream) {
     if (!ix || n < 0 || row0 < 0) return fail(MIPS_E_INVALID, "mips_index_add_synthetic: bad argument");
     if (kind < 0 || kind > 2) return fail(MIPS_E_INVALID, "mips_index_add_synthetic: unknown kind %d", kind);
+    if (ix->sq8) return fail(MIPS_E_UNSUPPORTED, "mips_index_add_synthetic: not served on an SQ8 index (mips_synth_fill + mips_index_add)");
     if (n == 0) return MIPS_OK;
     if (ix->ntotal + n > (int64_t)0x7fffff00) return fail(MIPS_E_UNSUPPORTED, "more than 2^31 rows on one GPU");
     DeviceGuard g(ix->device);
@@ -400,7 +412,13 @@ int search_call(mips_index* ix, SearchCall& c, SearchReport& rep, const void* q,
             if (nq_pad > nq) HIP_TRY(hipMemsetAsync(qb + (size_t)nq * row_bytes, 0, (size_t)(nq_pad - nq) * row_bytes, st));
             HIP_TRY(hipMemsetAsync(ix->cur.gthr.p, 0, (size_t)thr_words * sizeof(unsigned), st));
         } else { // one launch converts the queries, zero-pads to the tile multiple and clears the bounds
-            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, nullptr, nq_pad - nq, (uint32_t*)ix->cur.gthr.p, thr_words, ix->qsize);
+            if (ix->sq8) { // (the same launch writes B_q of every query)
+                rc = ix->cur.qbias.ensure((size_t)nq * sizeof(double));
+                if (rc) return rc;
+                c.qbias = (const double*)ix->cur.qbias.p;
+            }
+            rc = convert_into(ix, q, nq, q_dtype, q_dev, qb, st, nullptr, nq_pad - nq, (uint32_t*)ix->cur.gthr.p, thr_words, ix->qsize,
+                              (double*)ix->cur.qbias.p);
             if (rc) return rc;
         }
         c.qbuf = ix->cur.qbuf.p;
@@ -427,6 +445,11 @@ int search_call(mips_index* ix, SearchCall& c, SearchReport& rep, const void* q,
         default: rc = scan_and_finish<32>(ix, c, rep, pol, nq, k, d_s, d_i, packed, idx_offset, out_dev, st, tail_st, split); break;
         }
         if (rc) return rc;
+        if (ix->sq8) { // every writer of the [nq, k] scores is done on the stream of the tail: S -> D = S + B_q there
+            rc = sq8_finish(c, d_s, d_i, packed, nq, k, tail_st);
+            if (rc) return rc;
+            if (split) HIP_TRY(hipEventRecord(ix->cur.tail_done, tail_st)); // (supersedes the record behind the re-score)
+        }
     }
     if (!out_dev) {
         HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -457,6 +480,7 @@ int search_impl(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, int k,
 // ---- The wide and the range search (and their filtered / grouped forms) validate the same way and build the same Selector
 // what both serve: bf16 and fp32-exact indexes of up to 1024 columns, float32 or bf16 queries
 int check_served(const char* who, const mips_index* ix, int q_dtype) {
+    if (ix->sq8) return fail(MIPS_E_UNSUPPORTED, "%s: SQ8 storage is not served (bf16 and fp32-exact indexes only)", who);
     if (ix->esize == 1) return fail(MIPS_E_UNSUPPORTED, "%s: e4m3 storage is not served (bf16 and fp32-exact indexes only)", who);
     if ((ix->plane > 0 ? ix->plane : ix->ld) > 1024 || ix->d > 1024)
         return fail(MIPS_E_UNSUPPORTED, "%s: stored rows of more than 1024 columns are not served", who);
@@ -817,7 +841,7 @@ int mips_index_reconstruct(mips_index_t* ix, const int64_t* ids, int64_t n, int6
     if (!ix) return fail(MIPS_E_INVALID, "mips_index_reconstruct: index is NULL");
     if (n < 0 || out_ld < ix->d) return fail(MIPS_E_INVALID, "mips_index_reconstruct: n = %lld, out_ld = %lld for rows of %lld columns", (long long)n,
                                              (long long)out_ld, (long long)ix->d);
-    const int raw_dtype = ix->plane > 0 ? MIPS_DTYPE_F32 : ix->esize == 2 ? MIPS_DTYPE_BF16 : MIPS_DTYPE_FP8_E4M3;
+    const int raw_dtype = ix->plane > 0 ? MIPS_DTYPE_F32 : ix->esize == 2 ? MIPS_DTYPE_BF16 : ix->sq8 ? MIPS_DTYPE_SQ8 : MIPS_DTYPE_FP8_E4M3;
     if (out_dtype != MIPS_DTYPE_F32 && out_dtype != raw_dtype)
         return fail(MIPS_E_INVALID, "mips_index_reconstruct: out_dtype must be F32 (decoded) or the storage's element type %d (raw), got %d", raw_dtype,
                     out_dtype);
@@ -844,6 +868,7 @@ int mips_score_subset(mips_index_t* ix, const void* q, int q_dtype, int64_t nq, 
     if (!ix) return fail(MIPS_E_INVALID, "mips_score_subset: index is NULL");
     if (nq < 0 || k < 0) return fail(MIPS_E_INVALID, "mips_score_subset: negative nq or k");
     if (!src_dtype_ok(ix, q_dtype, true)) return fail(MIPS_E_INVALID, "mips_score_subset: q_dtype must be F32 or BF16 (or FP8_E4M3 bytes for an all-e4m3 index)");
+    if (ix->sq8 && !ix->sq8_trained) return fail(MIPS_E_INVALID, "mips_score_subset: the SQ8 index is not trained (mips_index_sq8_train)");
     if (nq == 0 || k == 0) return MIPS_OK;
     if (!q || !ids || !out_scores) return fail(MIPS_E_INVALID, "mips_score_subset: NULL buffer");
     if (nq > (1 << 24)) return fail(MIPS_E_UNSUPPORTED, "mips_score_subset: more than 2^24 queries in one call");

@@ -16,7 +16,8 @@ The reference never calls its search code directly: it goes through HF `datasets
 lands in `MipsIndex` (fp32-exact storage by default: `DEFAULT_DTYPE`).  HF's own hook works as well without any of this:
 `Dataset.add_faiss_index(column=..., custom_index=MipsIndex(d, metric))` -- it only needs `faiss` importable for its check.
 
-Exact ("Flat") indexes only: every other factory string raises NotImplementedError, like Mips.build_index.
+Exact indexes only -- "Flat", and "SQ8" storage (IndexScalarQuantizer, QT_8bit): every other factory string raises
+NotImplementedError, like Mips.build_index.
 
 L2: the reference only ever puts phi-AUGMENTED vectors into an L2 index (augment_xb, mips.py:59-65, 316-331): rows of constant
 norm sqrt(phi) whose last column is sqrt(phi - |x|^2), queries with a zero last column.  `IndexFlat(d + 1, METRIC_L2)` checks
@@ -342,14 +343,46 @@ class IndexFlatL2(IndexFlat):
         super().__init__(d, METRIC_L2)
 
 
+class ScalarQuantizer:
+    """faiss.ScalarQuantizer: the one quantiser type this backend stores."""
+    QT_8bit = 0
+
+
+class IndexScalarQuantizer(IndexFlat):
+    """faiss.IndexScalarQuantizer(d, ScalarQuantizer.QT_8bit, metric): one byte per element, 256 uniform levels over each
+    column's trained range (MipsIndex dtype "sq8").  train(x) before add(x); inner product only."""
+
+    def __init__(self, d: int, qtype: int = ScalarQuantizer.QT_8bit, metric: int = METRIC_L2, device: int = None):
+        if qtype != ScalarQuantizer.QT_8bit:
+            raise NotImplementedError(f"IndexScalarQuantizer: quantiser type {qtype!r}: QT_8bit only")
+        if metric != METRIC_INNER_PRODUCT:
+            raise NotImplementedError("IndexScalarQuantizer: inner product only -- this backend's L2 is the MIPS->L2 reduction over rows "
+                                      "of constant norm, which decoded SQ8 rows are not")
+        super().__init__(d, metric, dtype="sq8", device=device)
+
+    @property
+    def is_trained(self) -> bool:
+        return self._index().is_trained
+
+    def train(self, x=None) -> None:
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2 or x.shape[1] != self.d:
+            raise ValueError(f"train: expected [n, {self.d}], got {x.shape}")
+        self._index().train(x)
+
+
 Index = IndexFlat   # (type annotations in HF spell `faiss.Index`)
 
 
 def index_factory(d: int, description: str, metric: int = METRIC_L2) -> IndexFlat:
-    """faiss.index_factory for the one exact factory string the reference ships with (mips_string_factory = "Flat")."""
-    if description != "Flat":
-        raise NotImplementedError(f"index_factory({description!r}): only the exact 'Flat' index is implemented")
-    return IndexFlat(d, metric)
+    """faiss.index_factory: "Flat" (what the reference ships with, mips_string_factory) and "SQ8" (the storage half of its
+    "IVF256,SQ8" configuration).  The index is exact: IVF, HNSW and PQ -- alone or in front of a storage -- are refused."""
+    if description == "Flat":
+        return IndexFlat(d, metric)
+    if description == "SQ8":
+        return IndexScalarQuantizer(d, ScalarQuantizer.QT_8bit, metric)
+    raise NotImplementedError(f"index_factory({description!r}): the exact 'Flat' index and 'SQ8' storage are implemented "
+                              "(no IVF, HNSW or PQ: every search is exact)")
 
 
 # ---- write_index / read_index as HF drives them: faiss.write_index(index, faiss.BufferedIOWriter(faiss.PyCallbackIOWriter(f.write)))
@@ -384,6 +417,8 @@ def write_index(index: IndexFlat, writer) -> None:
     inner = index._index()
     head = {"d": index.d, "metric": index.metric_type, "dtype": inner.dtype, "ntotal": inner.ntotal, "inner_d": inner.d,
             "phi_seen": getattr(index, "_phi_seen", None)}
+    if inner.dtype == "sq8" and inner.is_trained:   # float32 parameters as exact hexadecimal strings
+        head["sq8_vmin"], head["sq8_vdiff"] = ([float(v).hex() for v in a] for a in inner.sq8_params())
     hb = json.dumps(head).encode()
     writer.write(_MAGIC + struct.pack("<q", len(hb)) + hb)
     for r0 in range(0, inner.ntotal, 1 << 16):
@@ -408,11 +443,16 @@ def read_index(reader) -> IndexFlat:
         raise ValueError("read_index: not an index written by this backend's write_index")
     (hl,) = struct.unpack("<q", _read_exact(reader, 8))
     head = json.loads(_read_exact(reader, hl))
-    index = IndexFlat(head["d"], head["metric"], dtype=head["dtype"])
+    if head["dtype"] == "sq8":
+        index = IndexScalarQuantizer(head["d"], ScalarQuantizer.QT_8bit, head["metric"])
+    else:
+        index = IndexFlat(head["d"], head["metric"], dtype=head["dtype"])
     if head.get("phi_seen") is not None:
         index._phi_seen = head["phi_seen"]
     inner = index._index()
-    npdt = {"bf16": np.uint16, "fp8_e4m3": np.uint8, "fp8_e4m3_docs": np.uint8, "f32": np.float32}[head["dtype"]]
+    if head.get("sq8_vmin") is not None:
+        inner.set_sq8_params([float.fromhex(v) for v in head["sq8_vmin"]], [float.fromhex(v) for v in head["sq8_vdiff"]])
+    npdt = {"bf16": np.uint16, "fp8_e4m3": np.uint8, "fp8_e4m3_docs": np.uint8, "f32": np.float32, "sq8": np.uint8}[head["dtype"]]
     row_bytes = head["inner_d"] * np.dtype(npdt).itemsize
     inner.reserve(head["ntotal"])
     for r0 in range(0, head["ntotal"], 1 << 16):

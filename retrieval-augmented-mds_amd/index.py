@@ -77,17 +77,26 @@ def route_search(index, q, k: int, **kwargs):
     return index.search(q, k, **kwargs)
 
 
+# file extension and element type of the stored rows, by index dtype (save / load)
+_ROWS_FILE = {"bf16": ("bf16", np.uint16), "fp8_e4m3": ("e4m3", np.uint8), "fp8_e4m3_docs": ("e4m3", np.uint8), "f32": ("f32", np.float32),
+              "sq8": ("sq8", np.uint8)}
+
+
 class MipsIndex:
     def __init__(self, d: int, metric: int = _lib.METRIC_IP, dtype: str = "bf16", device: int | None = None):
-        if dtype not in ("bf16", "fp8_e4m3", "fp8_e4m3_docs", "f32"):
+        if dtype not in ("bf16", "fp8_e4m3", "fp8_e4m3_docs", "f32", "sq8"):
             raise NotImplementedError(f"index dtype {dtype!r}: this build stores 'bf16', 'fp8_e4m3' (queries e4m3 too), "
-                                      "'fp8_e4m3_docs' (e4m3 rows, bf16 queries) or 'f32'")
+                                      "'fp8_e4m3_docs' (e4m3 rows, bf16 queries), 'sq8' (trained 8-bit codes) or 'f32'")
+        if dtype == "sq8" and int(metric) != _lib.METRIC_IP:
+            raise NotImplementedError("an 'sq8' index ranks by inner product only: the L2 rule |q|^2 + phi - 2 q.x presumes rows of "
+                                      "constant norm, which decoded SQ8 rows are not")
         self._lib = _lib.load()
         self.device = _lib.require_gpu(device)
         self._h = ctypes.c_void_p()
         self._code = {"bf16": _lib.DTYPE_BF16, "fp8_e4m3": _lib.DTYPE_FP8_E4M3, "fp8_e4m3_docs": _lib.DTYPE_FP8_E4M3_DOCS,
-                      "f32": _lib.DTYPE_F32}[dtype]
+                      "f32": _lib.DTYPE_F32, "sq8": _lib.DTYPE_SQ8}[dtype]
         self._f8 = self._code in (_lib.DTYPE_FP8_E4M3, _lib.DTYPE_FP8_E4M3_DOCS)   # e4m3 storage
+        self._sq8 = self._code == _lib.DTYPE_SQ8   # trained 8-bit codes (faiss "SQ8"): train() before add()
         _lib.check(self._lib.mips_index_create(ctypes.byref(self._h), self.device, int(d), self._code,
                                                int(metric)), "mips_index_create")
         self._d = int(d)
@@ -110,7 +119,10 @@ class MipsIndex:
     def metric_type(self) -> int:
         return self._metric
 
-    is_trained = True
+    @property
+    def is_trained(self) -> bool:
+        """faiss Index.is_trained: False only on an 'sq8' index before train() / set_sq8_params()."""
+        return not self._sq8 or self._lib.mips_index_sq8_is_trained(self._h) == 1
 
     def __len__(self) -> int:
         return self.ntotal
@@ -138,6 +150,10 @@ class MipsIndex:
                 code = _lib.DTYPE_BF16
             elif x.dtype == getattr(torch, "float8_e4m3fn", None) and self._f8 and not (what == "search" and self._code == _lib.DTYPE_FP8_E4M3_DOCS):
                 code = _lib.DTYPE_FP8_E4M3  # raw e4m3 bytes
+            elif x.dtype == torch.uint8 and self._sq8:
+                if what != "add":
+                    raise ValueError(f"{what}: an 'sq8' index takes float32 / bfloat16 queries; uint8 codes are rows only")
+                code = _lib.DTYPE_SQ8  # raw codes
             else:
                 x = x.float()
                 code = _lib.DTYPE_F32
@@ -156,6 +172,11 @@ class MipsIndex:
         if a.dtype == np.uint8 and self._f8 and not (what == "search" and self._code == _lib.DTYPE_FP8_E4M3_DOCS):  # raw e4m3 codes
             a = np.ascontiguousarray(a)
             return a.ctypes.data, _lib.DTYPE_FP8_E4M3, 0, a.shape[0], a
+        if a.dtype == np.uint8 and self._sq8:
+            if what != "add":
+                raise ValueError(f"{what}: an 'sq8' index takes float32 queries; uint8 codes are rows only")
+            a = np.ascontiguousarray(a)
+            return a.ctypes.data, _lib.DTYPE_SQ8, 0, a.shape[0], a  # raw codes
         a = np.ascontiguousarray(a, dtype=np.float32)
         return a.ctypes.data, _lib.DTYPE_F32, 0, a.shape[0], a
 
@@ -163,9 +184,44 @@ class MipsIndex:
     def reserve(self, n: int) -> None:
         _lib.check(self._lib.mips_index_reserve(self._h, int(n)), "mips_index_reserve")
 
+    def train(self, x) -> None:
+        """faiss Index.train.  An 'sq8' index learns its per-column range from x [n, d] (float32 / bfloat16, host or device:
+        vmin = column minimum, vdiff = column maximum - vmin; NaN or infinite values and n = 0 raise) and must be trained
+        before add(); training again is possible while the index is empty.  Every other storage has nothing to train."""
+        if not self._sq8:
+            return
+        ptr, code, is_dev, n, keep = self._as_buffer(x, "train")
+        with self._mutex:
+            _lib.check(self._lib.mips_index_sq8_train(self._h, ptr, n, code, _lib.Q_DEVICE if is_dev else 0, _stream_handle(self.device)),
+                       "mips_index_sq8_train")
+        del keep
+
+    def sq8_params(self):
+        """(vmin, vdiff): the trained per-column range of an 'sq8' index, np.float32 [d] each."""
+        if not self._sq8:
+            raise TypeError("sq8_params: not an 'sq8' index")
+        vmin, vdiff = np.empty(self._d, np.float32), np.empty(self._d, np.float32)
+        with self._mutex:
+            _lib.check(self._lib.mips_index_sq8_get_params(self._h, vmin.ctypes.data, vdiff.ctypes.data), "mips_index_sq8_get_params")
+        return vmin, vdiff
+
+    def set_sq8_params(self, vmin, vdiff) -> None:
+        """Set the per-column range of an EMPTY 'sq8' index instead of training it (load does; finite values, vdiff >= 0)."""
+        if not self._sq8:
+            raise TypeError("set_sq8_params: not an 'sq8' index")
+        vmin = np.ascontiguousarray(np.asarray(vmin, dtype=np.float32).reshape(-1))
+        vdiff = np.ascontiguousarray(np.asarray(vdiff, dtype=np.float32).reshape(-1))
+        if vmin.shape != (self._d,) or vdiff.shape != (self._d,):
+            raise ValueError(f"set_sq8_params: expected two arrays of {self._d}")
+        with self._mutex:
+            _lib.check(self._lib.mips_index_sq8_set_params(self._h, vmin.ctypes.data, vdiff.ctypes.data), "mips_index_sq8_set_params")
+
     def add(self, x) -> None:
         """faiss Index.add: append rows (np.float32 / np.uint16 bf16 bits / torch float32|bfloat16,
-        host or device).  float32 is rounded to bf16 (RNE) on the device."""
+        host or device).  float32 is rounded to bf16 (RNE) on the device.  An 'sq8' index encodes with its trained range
+        (np.uint8 / torch.uint8: raw codes) and raises before train()."""
+        if self._sq8 and not self.is_trained:
+            raise RuntimeError("add: the 'sq8' index is not trained (train(x) first, as faiss requires)")
         ptr, code, is_dev, n, keep = self._as_buffer(x, "add")
         with self._mutex:
             _lib.check(self._lib.mips_index_add(self._h, ptr, n, code, is_dev, _stream_handle(self.device)),
@@ -260,7 +316,7 @@ class MipsIndex:
     def rows_raw(self, row0: int = 0, n: int | None = None) -> np.ndarray:
         """Stored rows in the index dtype: np.uint16 bf16 bits, np.uint8 e4m3 codes or np.float32, [n, d]."""
         n = self.ntotal - row0 if n is None else n
-        npdt = {_lib.DTYPE_BF16: np.uint16, _lib.DTYPE_FP8_E4M3: np.uint8, _lib.DTYPE_FP8_E4M3_DOCS: np.uint8, _lib.DTYPE_F32: np.float32}[self._code]
+        npdt = self._RAW_NP[self._code]
         out = np.empty((n, self._d), dtype=npdt)
         _lib.check(self._lib.mips_index_read_rows(self._h, int(row0), int(n), out.ctypes.data,
                                                   _stream_handle(self.device)), "mips_index_read_rows")
@@ -277,7 +333,8 @@ class MipsIndex:
         return out
 
     # ------------------------------------------------------------------ rows by id (include/mips_hip_rows.h)
-    _RAW_NP = {_lib.DTYPE_BF16: np.uint16, _lib.DTYPE_FP8_E4M3: np.uint8, _lib.DTYPE_FP8_E4M3_DOCS: np.uint8, _lib.DTYPE_F32: np.float32}
+    _RAW_NP = {_lib.DTYPE_BF16: np.uint16, _lib.DTYPE_FP8_E4M3: np.uint8, _lib.DTYPE_FP8_E4M3_DOCS: np.uint8, _lib.DTYPE_F32: np.float32,
+               _lib.DTYPE_SQ8: np.uint8}
 
     def _ids_arg(self, ids, what: str):
         """ids of any shape (NumPy / sequence -> host, CUDA tensor -> device) -> (pointer, shape, is_device, keepalive)."""
@@ -316,7 +373,7 @@ class MipsIndex:
         out_dtype = _lib.DTYPE_F32 if not raw else (_lib.DTYPE_FP8_E4M3 if self._f8 else self._code)
         flags = _lib.ROWS_ZERO_MISSING if zero_missing else 0
         if is_dev:
-            tdt = torch.float32 if (not raw or self._code == _lib.DTYPE_F32) else torch.uint8 if self._f8 else torch.bfloat16
+            tdt = torch.float32 if (not raw or self._code == _lib.DTYPE_F32) else torch.uint8 if (self._f8 or self._sq8) else torch.bfloat16
             if out is None:
                 out = torch.empty(shape + (self._d,), dtype=tdt, device=f"cuda:{self.device}")
                 out_ld = self._d
@@ -385,6 +442,8 @@ class MipsIndex:
         -> a CUDA tensor (host ids are copied over first)."""
         import torch
 
+        if self._sq8 and not self.is_trained:
+            raise RuntimeError("compute_distance_subset: the 'sq8' index is not trained (train(x) first)")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
         if is_dev and not (isinstance(ids, torch.Tensor) and ids.is_cuda):
             ids = torch.as_tensor(np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids), dtype=torch.int64).to(f"cuda:{self.device}")
@@ -531,15 +590,15 @@ class MipsIndex:
             raise ValueError("k must be >= 0")
         if k > _lib.MAX_K_WIDE:
             raise NotImplementedError(f"k = {k} > {_lib.MAX_K_WIDE} is not supported by this build")
-        if self._f8:
-            raise NotImplementedError("search_wide serves 'bf16' and 'f32' indexes; e4m3 storage is limited to search()")
+        if self._f8 or self._sq8:
+            raise NotImplementedError("search_wide serves 'bf16' and 'f32' indexes; e4m3 and sq8 storage is limited to search()")
         if self._d > 1024:
             raise NotImplementedError("search_wide serves rows of at most 1024 columns")
 
     # ------------------------------------------------------------------ range search
     def _check_range(self) -> None:
-        if self._f8:
-            raise NotImplementedError("range_search serves 'bf16' and 'f32' indexes; e4m3 storage is limited to search()")
+        if self._f8 or self._sq8:
+            raise NotImplementedError("range_search serves 'bf16' and 'f32' indexes; e4m3 and sq8 storage is limited to search()")
         if self._d > 1024:
             raise NotImplementedError("range_search serves rows of at most 1024 columns")
 
@@ -677,8 +736,8 @@ class MipsIndex:
 
         k = int(k)
         if groups is not None:  # (the storages and widths the grouped wide search serves)
-            if self._f8:
-                raise NotImplementedError("search_fused(groups=) serves 'bf16' and 'f32' indexes, not e4m3 storage")
+            if self._f8 or self._sq8:
+                raise NotImplementedError("search_fused(groups=) serves 'bf16' and 'f32' indexes, not e4m3 or sq8 storage")
             if self._d > 1024:
                 raise NotImplementedError("search_fused(groups=) serves rows of at most 1024 columns")
         ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
@@ -784,13 +843,14 @@ class MipsIndex:
     # ------------------------------------------------------------------ persistence
     # Own format (the on-disk format is free, the call surface is kept):
     #   <path>/meta.json   {"format":1,"d":..,"ntotal":..,"metric":..,"dtype":"bf16", ...}
-    #   <path>/rows.bf16   raw little-endian bf16 bit patterns [ntotal, d]   (rows.e4m3: e4m3 bytes)
+    #   <path>/rows.bf16   raw little-endian bf16 bit patterns [ntotal, d]   (rows.e4m3: e4m3 bytes; rows.sq8: codes, with
+    #                      "sq8_vmin" / "sq8_vdiff" in meta.json: the float32 parameters as exact hexadecimal strings)
     #   <path>/labels.i32  little-endian int32 [ntotal], only with "labels": true in meta.json (a fully labelled index)
     def save(self, path: str, extra: dict | None = None, chunk_rows: int = 1 << 16) -> None:
         """Replaces Dataset.save_faiss_index (sotasum/mips.py:536)."""
         os.makedirs(path, exist_ok=True)
         n = self.ntotal
-        with open(os.path.join(path, "rows." + {"bf16": "bf16", "fp8_e4m3": "e4m3", "fp8_e4m3_docs": "e4m3", "f32": "f32"}[self.dtype]), "wb") as f:
+        with open(os.path.join(path, "rows." + _ROWS_FILE[self.dtype][0]), "wb") as f:
             for r0 in range(0, n, chunk_rows):
                 f.write(self.rows_raw(r0, min(chunk_rows, n - r0)).tobytes())
         meta = {"format": _FORMAT_VERSION, "d": self._d, "ntotal": n, "metric": self._metric, "dtype": self.dtype}
@@ -798,6 +858,9 @@ class MipsIndex:
             # phi of the WHOLE file: a rank that loads one row range of it must not fall back to its own rows' maximum
             # (L2 distances of different shards would not be comparable)
             meta["phi"] = self.phi()
+        if self._sq8 and self.is_trained:
+            vmin, vdiff = self.sq8_params()
+            meta["sq8_vmin"], meta["sq8_vdiff"] = [float(v).hex() for v in vmin], [float(v).hex() for v in vdiff]
         if n > 0 and self._nlabelled == n:
             with open(os.path.join(path, "labels.i32"), "wb") as f:
                 f.write(self.labels().astype("<i4").tobytes())
@@ -819,9 +882,10 @@ class MipsIndex:
         ix = cls(meta["d"], metric=meta["metric"], dtype=meta["dtype"], device=device)
         n, d = meta["ntotal"], meta["d"]
         lo, hi = (0, n) if row_range is None else row_range
+        if meta.get("sq8_vmin") is not None:  # (the whole file's parameters, whichever row range is loaded)
+            ix.set_sq8_params([float.fromhex(v) for v in meta["sq8_vmin"]], [float.fromhex(v) for v in meta["sq8_vdiff"]])
         if hi > lo:
-            ext, npdt = {"bf16": ("bf16", np.uint16), "fp8_e4m3": ("e4m3", np.uint8), "fp8_e4m3_docs": ("e4m3", np.uint8),
-                         "f32": ("f32", np.float32)}[meta["dtype"]]
+            ext, npdt = _ROWS_FILE[meta["dtype"]]
             mm = np.memmap(os.path.join(path, "rows." + ext), dtype=npdt, mode="r", shape=(n, d))
             ix.reserve(hi - lo)
             for r0 in range(lo, hi, chunk_rows):

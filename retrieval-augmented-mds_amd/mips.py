@@ -202,6 +202,16 @@ class _IndexHolder:
         self.faiss_index = index
 
 
+def factory_dtype(string_factory, dtype: str) -> str:
+    """The storage dtype a faiss factory string asks for: None / "Flat" keep `dtype`, "SQ8" is the trained 8-bit scalar quantiser
+    ('sq8', inner product only).  Everything else -- IVF, HNSW, PQ, other quantiser types -- is refused: the index is exact."""
+    if string_factory in (None, "Flat"):
+        return dtype
+    if string_factory == "SQ8":
+        return "sq8"
+    raise NotImplementedError(f"string_factory={string_factory!r}: the exact 'Flat' index and 'SQ8' storage are implemented")
+
+
 class KnowledgeBase:
     """The few Dataset operations the path uses on `self.embeddings`: row fetch by id
     (`embeddings[i][text_column]`, mips.py:428, 458), get_index (mips.py:383) and len."""
@@ -275,14 +285,16 @@ class KnowledgeBase:
             the un-augmented d = d' - 1 columns and reproduces the augmented distances |q|^2 + phi - 2 q.x, so a
             constant-norm column is stripped of its last element; any other L2 column is refused (plain L2 on rows
             of different norms is not this path)."""
-        if string_factory not in (None, "Flat"):
-            raise NotImplementedError(f"string_factory={string_factory!r}: only the exact 'Flat' index is implemented")
+        dtype = factory_dtype(string_factory, dtype)   # "SQ8": trained on the first train_size rows (all if None), as HF does
         index_name = index_name if index_name is not None else column
         if custom_index is not None:
             self._indexes[index_name] = _IndexHolder(custom_index)
             self._index_columns[index_name] = column
             return self
         metric = METRIC_L2 if metric_type is None else int(metric_type)
+        if dtype == "sq8" and metric != METRIC_INNER_PRODUCT:
+            raise NotImplementedError("add_faiss_index(string_factory='SQ8'): inner product only -- this backend's L2 is the MIPS->L2 "
+                                      "reduction over rows of constant norm, which decoded SQ8 rows are not")
         x = np.asarray(self.columns[column], dtype=np.float32)
         if x.ndim != 2:
             raise ValueError(f"add_faiss_index: column {column!r} must be a matrix [N, d], got shape {x.shape}")
@@ -298,6 +310,8 @@ class KnowledgeBase:
         elif metric != METRIC_INNER_PRODUCT:
             raise NotImplementedError(f"metric_type={metric_type!r}: inner product (0) and L2 (1) only")
         index = MipsIndex(x.shape[1], metric=metric, dtype=dtype, device=device)
+        if dtype == "sq8":
+            index.train(x if train_size is None else x[:int(train_size)])
         index.reserve(x.shape[0])
         for r0 in range(0, x.shape[0], max(int(batch_size), 1 << 16)):  # HF adds in batches; rows are converted on the device
             index.add(x[r0:r0 + max(int(batch_size), 1 << 16)])
@@ -525,9 +539,7 @@ class Mips:
         other ranks return at once and pick the index up in load()."""
         import torch
 
-        if self.string_factory not in (None, "Flat"):
-            raise NotImplementedError(
-                f"mips_string_factory={self.string_factory!r}: only the exact 'Flat' index is implemented")
+        dtype = factory_dtype(self.string_factory, self.args.mips_index_dtype)
         rank, world, up = self._dist()
         if up and rank != 0:
             return
@@ -548,8 +560,10 @@ class Mips:
         if self.normalize and self.metric_type == METRIC_INNER_PRODUCT:
             l2_normalize_(x)
 
-        index = MipsIndex(x.shape[1], metric=self.metric_type, dtype=self.args.mips_index_dtype,
-                          device=self.args.mips_device)
+        index = MipsIndex(x.shape[1], metric=self.metric_type, dtype=dtype, device=self.args.mips_device)
+        if dtype == "sq8":   # mips_train_size rows (mips.py:333-340 passes it as train_size), all of them when it is not positive
+            ts = self.train_size if isinstance(self.train_size, int) and self.train_size > 0 else x.shape[0]
+            index.train(x[:ts])
         index.reserve(x.shape[0])
         index.add(x)
         if self.metric_type == METRIC_L2:
@@ -563,9 +577,9 @@ class Mips:
     # exchange (mips.py:243-244, 292-295), no second pass: max-norm is a running maximum, the IP normalisation is per
     # row, phi is taken from the finished index -- the result is bit-identical to build_index(all rows at once)
     def begin_index_build(self, d: int) -> None:
-        if self.string_factory not in (None, "Flat"):
-            raise NotImplementedError(
-                f"mips_string_factory={self.string_factory!r}: only the exact 'Flat' index is implemented")
+        if factory_dtype(self.string_factory, self.args.mips_index_dtype) == "sq8":
+            raise NotImplementedError("mips_string_factory='SQ8': the streaming build has no rows to train on before the first add; "
+                                      "build_index() trains and adds")
         self._building = {"index": MipsIndex(int(d), metric=self.metric_type, dtype=self.args.mips_index_dtype,
                                              device=self.args.mips_device),
                           "max_sq": None, "cols": {}, "rows": 0}   # max_sq: one float64 ON THE DEVICE, read once in end_index_build
@@ -624,15 +638,12 @@ class Mips:
 
         from .sharded import ShardedMipsIndex
 
-        if self.string_factory not in (None, "Flat"):
-            raise NotImplementedError(
-                f"mips_string_factory={self.string_factory!r}: only the exact 'Flat' index is implemented")
+        dtype = factory_dtype(self.string_factory, self.args.mips_index_dtype)   # ("SQ8": ShardedMipsIndex refuses it)
         n = len(embeddings)
         if isinstance(self.args.mips_db_max_size, int):
             n = min(n, self.args.mips_db_max_size)
         dev_id = _lib.require_gpu(self.args.mips_device)
-        sh = ShardedMipsIndex(int(np.shape(embeddings)[1]), metric=self.metric_type, dtype=self.args.mips_index_dtype,
-                              device=dev_id)
+        sh = ShardedMipsIndex(int(np.shape(embeddings)[1]), metric=self.metric_type, dtype=dtype, device=dev_id)
         lo, hi = sh.set_global_size(n)
         x = torch.as_tensor(np.ascontiguousarray(embeddings[lo:hi], dtype=np.float32)
                             if not isinstance(embeddings, torch.Tensor) else embeddings[lo:hi]).to(f"cuda:{dev_id}", dtype=torch.float32).contiguous()

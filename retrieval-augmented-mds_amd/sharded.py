@@ -91,6 +91,9 @@ class ShardedMipsIndex:
                  local_reconstruct=None):
         import torch.distributed as dist
 
+        if dtype == "sq8":
+            raise NotImplementedError("ShardedMipsIndex: 'sq8' storage is not served -- every shard would train its own column range, "
+                                      "and scores of different ranges do not merge (a global min / max is not implemented)")
         self.d = int(d)
         self.metric_type = int(metric)
         self.group = group

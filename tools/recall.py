@@ -44,8 +44,9 @@ for kind in ("gauss", "clustered"):
         ref.check()
         ti = ti.cpu().numpy()
         del ref
-        for dtype in ("bf16", "fp8_e4m3", "fp8_e4m3_docs"):    # (the last: e4m3 rows, bf16 queries)
+        for dtype in ("bf16", "fp8_e4m3", "fp8_e4m3_docs", "sq8"):    # (e4m3 rows, bf16 queries; trained 8-bit codes, bf16 queries)
             ix = ram.MipsIndex(a.dim, dtype=dtype)
+            ix.train(x)    # ("sq8": the per-column range of the rows themselves; nothing to train otherwise)
             ix.add(x)
             _, gi = ix.search(q, a.k)
             ix.check()
