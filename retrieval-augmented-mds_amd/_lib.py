@@ -23,6 +23,7 @@ HEADER_UPDATE = os.path.join(_ROOT, "include", "mips_hip_update.h")  # calls tha
 HEADER_ROWS = os.path.join(_ROOT, "include", "mips_hip_rows.h")  # stored rows, labels and scores by row id
 HEADER_HOOK = os.path.join(_ROOT, "include", "mips_hip_hook.h")  # the one-launch hook search under a group filter
 HEADER_SQ8 = os.path.join(_ROOT, "include", "mips_hip_sq8.h")  # the trained 8-bit scalar quantiser of an SQ8 index
+HEADER_IVF = os.path.join(_ROOT, "include", "mips_hip_ivf.h")  # the IVF index: k-means lists over a flat index, nprobe
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -43,7 +44,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -160,7 +161,25 @@ def _bind(lib):
         "mips_index_sq8_get_params": (i32, [vp, vp, vp]),
         "mips_index_sq8_is_trained": (i32, [vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8}.items():
+    sig_ivf = {  # include/mips_hip_ivf.h
+        "mips_ivf_create": (i32, [c.POINTER(vp), i32, i64, i32, i32, i64]),
+        "mips_ivf_destroy": (i32, [vp]),
+        "mips_ivf_flat": (vp, [vp]),
+        "mips_ivf_train": (i32, [vp, vp, i64, i32, i32, vp]),
+        "mips_ivf_is_trained": (i32, [vp]),
+        "mips_ivf_set_centroids": (i32, [vp, vp]),
+        "mips_ivf_get_centroids": (i32, [vp, vp]),
+        "mips_ivf_add": (i32, [vp, vp, i64, i32, i32, vp]),
+        "mips_ivf_probe": (i32, [vp, vp, i32, i64, i64, vp, i32, vp]),
+        "mips_ivf_remove": (i32, [vp, vp, i64, i64, i32, c.POINTER(i64), vp]),
+        "mips_ivf_reset": (i32, [vp]),
+        "mips_ivf_list_sizes": (i32, [vp, vp, vp]),
+        "mips_ivf_read_assign": (i32, [vp, i64, i64, vp, vp]),
+        "mips_ivf_set_assign": (i32, [vp, vp, i64, vp]),
+        "mips_ivf_set_param": (i32, [vp, c.c_char_p, i64]),
+        "mips_ivf_nlist": (i64, [vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -184,6 +203,9 @@ EXPORTS_UPDATE = ("mips_index_remove",)  # what include/mips_hip_update.h declar
 EXPORTS_ROWS = ("mips_index_reconstruct", "mips_index_gather_labels", "mips_score_subset")  # include/mips_hip_rows.h, likewise
 EXPORTS_HOOK = ("mips_search_fused_grp",)  # include/mips_hip_hook.h, likewise
 EXPORTS_SQ8 = ("mips_index_sq8_train", "mips_index_sq8_set_params", "mips_index_sq8_get_params", "mips_index_sq8_is_trained")  # mips_hip_sq8.h
+EXPORTS_IVF = ("mips_ivf_create", "mips_ivf_destroy", "mips_ivf_flat", "mips_ivf_train", "mips_ivf_is_trained", "mips_ivf_set_centroids",
+               "mips_ivf_get_centroids", "mips_ivf_add", "mips_ivf_probe", "mips_ivf_remove", "mips_ivf_reset",
+               "mips_ivf_list_sizes", "mips_ivf_read_assign", "mips_ivf_set_assign", "mips_ivf_set_param", "mips_ivf_nlist")  # mips_hip_ivf.h
 
 
 def range_record_words(nq: int, stride: int) -> int:

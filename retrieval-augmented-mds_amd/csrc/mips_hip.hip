@@ -22,6 +22,7 @@
 #include "../../include/mips_hip_rows.h"
 #include "../../include/mips_hip_hook.h"
 #include "../../include/mips_hip_sq8.h"
+#include "../../include/mips_hip_ivf.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -40,6 +41,7 @@
 #include "rows_kernels.hpp"
 #include "sq8_kernels.hpp"
 #include "sq8_scan_kernel.hpp"
+#include "ivf_kernels.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"
@@ -1086,3 +1088,5 @@ int mips_scan_timing(mips_index_t* ix, float* out_sum_ms, int* out_count, int re
 }
 
 } // extern "C"
+
+#include "host_ivf.hpp" // the IVF index (include/mips_hip_ivf.h): its own entry points, behind everything they call

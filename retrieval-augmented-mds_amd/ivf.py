@@ -1,0 +1,262 @@
+"""IvfIndex -- an inverted file (k-means lists, nprobe) over the rows of a flat index (include/mips_hip_ivf.h).
+
+What is here builds and maintains the file: deterministic k-means training, the list of every added row, the list table, the
+probed lists P(q) of a query, removal, reset, save / load.  The search over the probed lists is NOT in this build yet (DESIGN.md
+4j); `flat` is the inner MipsIndex over the same rows and searches them exactly.
+
+All arithmetic happens in libmips_hip.so; this file moves pointers.  No CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+import json
+import os
+import threading
+
+import numpy as np
+
+from . import _lib
+from .index import _FORMAT_VERSION, _ROWS_FILE, MipsIndex, _stream_handle
+
+_DTYPES = {"bf16": _lib.DTYPE_BF16, "f32": _lib.DTYPE_F32, "sq8": _lib.DTYPE_SQ8}
+
+
+class _FlatView(MipsIndex):
+    """The inner flat index of an IvfIndex, borrowed: reads (reconstruct*, labels, rows_raw, sq8_params, compute_distance_subset)
+    work unchanged; what would change its rows behind the list table is refused."""
+
+    def __init__(self, owner: "IvfIndex"):
+        self._lib = owner._lib
+        self.device = owner.device
+        self._h = ctypes.c_void_p(owner._lib.mips_ivf_flat(owner._h))
+        self._code = _DTYPES[owner.dtype]
+        self._f8 = False
+        self._sq8 = owner.dtype == "sq8"
+        self._d = owner.d
+        self._metric = _lib.METRIC_IP
+        self.dtype = owner.dtype
+        self.nprobe = 1
+        self._mutex = owner._mutex
+        self._nlabelled = 0
+        self._owner = owner  # (keeps the handle alive)
+
+    def __del__(self):  # borrowed: the IvfIndex destroys it
+        pass
+
+    def _refuse(self, *a, **kw):
+        raise RuntimeError("the inner flat index of an IvfIndex is changed through the IvfIndex (train / add / remove_ids / reset)")
+
+    train = add = add_synthetic = reset = remove_ids = reserve = _refuse
+
+
+class IvfIndex:
+    def __init__(self, d: int, nlist: int, dtype: str = "bf16", metric: int = _lib.METRIC_IP, device: int | None = None):
+        if dtype not in _DTYPES:
+            raise NotImplementedError(f"IvfIndex dtype {dtype!r}: 'bf16', 'f32' or 'sq8' (the e4m3 storages are not served)")
+        if int(metric) != _lib.METRIC_IP:
+            raise NotImplementedError("an IvfIndex ranks by inner product only (the index's L2 is the MIPS->L2 reduction)")
+        if int(d) > 1024:
+            raise NotImplementedError("IvfIndex: rows of more than 1024 columns are not served")
+        if not 1 <= int(nlist) <= 65536:
+            raise NotImplementedError(f"IvfIndex: nlist must be 1 .. 65536, got {nlist}")
+        self._lib = _lib.load()
+        self.device = _lib.require_gpu(device)
+        self._h = ctypes.c_void_p()
+        _lib.check(self._lib.mips_ivf_create(ctypes.byref(self._h), self.device, int(d), _DTYPES[dtype], int(metric), int(nlist)), "mips_ivf_create")
+        self._d, self._nlist, self.dtype = int(d), int(nlist), dtype
+        self.nprobe = 1  # lists probe() returns by default (faiss IndexIVF.nprobe)
+        self._niter = 10
+        self._mutex = threading.RLock()
+        self.flat = _FlatView(self)
+
+    # ------------------------------------------------------------------ faiss-like attributes
+    @property
+    def d(self) -> int:
+        return self._d
+
+    @property
+    def nlist(self) -> int:
+        return self._nlist
+
+    @property
+    def ntotal(self) -> int:
+        return self.flat.ntotal
+
+    @property
+    def metric_type(self) -> int:
+        return _lib.METRIC_IP
+
+    @property
+    def is_trained(self) -> bool:
+        return self._lib.mips_ivf_is_trained(self._h) == 1
+
+    @property
+    def niter(self) -> int:
+        return self._niter
+
+    @niter.setter
+    def niter(self, v: int) -> None:
+        _lib.check(self._lib.mips_ivf_set_param(self._h, b"ivf_niter", int(v)), "mips_ivf_set_param")
+        self._niter = int(v)
+
+    def __len__(self) -> int:
+        return self.ntotal
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self._lib.mips_ivf_destroy(h)
+            except Exception:
+                pass
+            h.value = None
+
+    def _rows(self, x, what: str):
+        """float32 / bfloat16 rows or queries, host or device -> (pointer, dtype code, is_device, n, keepalive)"""
+        import torch
+
+        if isinstance(x, torch.Tensor):
+            if x.dtype not in (torch.float32, torch.bfloat16):
+                if not x.dtype.is_floating_point:
+                    raise NotImplementedError(f"{what}: raw codes cannot be assigned to a list (float32 or bfloat16 values)")
+                x = x.float()
+        elif np.asarray(x).dtype.kind in "iub":
+            raise NotImplementedError(f"{what}: raw codes (uint8 SQ8 codes, uint16 bf16 bits) cannot be assigned to a list")
+        return self.flat._as_buffer(x, what)
+
+    # ------------------------------------------------------------------ building
+    def train(self, x) -> None:
+        """Deterministic k-means (include/mips_hip_ivf.h): niter iterations from evenly spaced initial rows; an 'sq8' index also
+        trains its per-column range on x.  Raises on n < nlist, on NaN / infinity and on an index that holds rows."""
+        ptr, code, is_dev, n, keep = self._rows(x, "train")
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_train(self._h, ptr, n, code, _lib.Q_DEVICE if is_dev else 0, _stream_handle(self.device)), "mips_ivf_train")
+        del keep
+
+    def centroids(self) -> np.ndarray:
+        out = np.empty((self._nlist, self._d), np.float32)
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_get_centroids(self._h, out.ctypes.data), "mips_ivf_get_centroids")
+        return out
+
+    def set_centroids(self, c) -> None:
+        """Plant the centroids (stored as given, not normalised) of an EMPTY index; an 'sq8' index needs flat.set_sq8_params too."""
+        c = np.ascontiguousarray(np.asarray(c, dtype=np.float32))
+        if c.shape != (self._nlist, self._d):
+            raise ValueError(f"set_centroids: expected [{self._nlist}, {self._d}], got {c.shape}")
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_set_centroids(self._h, c.ctypes.data), "mips_ivf_set_centroids")
+
+    def set_sq8_params(self, vmin, vdiff) -> None:
+        MipsIndex.set_sq8_params(self.flat, vmin, vdiff)
+
+    def add(self, x) -> None:
+        if not self.is_trained:
+            raise RuntimeError("add: the IvfIndex is not trained (train(x) first, as faiss requires)")
+        ptr, code, is_dev, n, keep = self._rows(x, "add")
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_add(self._h, ptr, n, code, is_dev, _stream_handle(self.device)), "mips_ivf_add")
+        del keep
+
+    def reset(self) -> None:
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_reset(self._h), "mips_ivf_reset")
+            self.flat._nlabelled = 0
+
+    def remove_ids(self, sel, sel_bit0: int = 0) -> int:
+        """faiss remove_ids: as MipsIndex.remove_ids; the assignments follow their rows and the list table is rebuilt."""
+        from .selector import Selector, is_id_list
+
+        sel_bit0 = int(sel_bit0)
+        with self._mutex:
+            if is_id_list(sel):
+                sel = Selector.from_ids(sel, sel_bit0 + self.ntotal, device=self.device)
+            ptr, nbits, flag, keep = self.flat._sel_args(sel, sel_bit0, "remove_ids")
+            counts = (ctypes.c_int64 * 2)()
+            _lib.check(self._lib.mips_ivf_remove(self._h, ptr, nbits, sel_bit0, flag, counts, _stream_handle(self.device)), "mips_ivf_remove")
+            self.flat._nlabelled = int(counts[1])
+        del keep
+        return int(counts[0])
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.empty(self._nlist, np.int64)
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_list_sizes(self._h, out.ctypes.data, _stream_handle(self.device)), "mips_ivf_list_sizes")
+        return out
+
+    def assignments(self) -> np.ndarray:
+        """int32 [ntotal]: the list of every row"""
+        out = np.empty(self.ntotal, np.int32)
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_read_assign(self._h, 0, out.shape[0], out.ctypes.data, _stream_handle(self.device)), "mips_ivf_read_assign")
+        return out
+
+    # ------------------------------------------------------------------ searching
+    def probe(self, x, nprobe: int | None = None) -> np.ndarray:
+        """P(q): int32 [nq, min(nprobe, nlist)], the probed lists of every query, nearest first."""
+        nprobe = int(self.nprobe if nprobe is None else nprobe)
+        ptr, code, is_dev, nq, keep = self._rows(x, "probe")
+        if nprobe < 1:
+            raise ValueError("nprobe must be >= 1")
+        out = np.empty((nq, min(nprobe, self._nlist)), np.int32)
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_probe(self._h, ptr, code, nq, nprobe, out.ctypes.data, _lib.Q_DEVICE if is_dev else 0,
+                                                _stream_handle(self.device)), "mips_ivf_probe")
+        del keep
+        return out
+
+    # rows by id: the inner flat index's (row ids are the flat ids)
+    def reconstruct(self, key: int):
+        return self.flat.reconstruct(key)
+
+    def reconstruct_n(self, n0: int = 0, ni: int | None = None):
+        return self.flat.reconstruct_n(n0, ni)
+
+    def reconstruct_batch(self, ids, **kw):
+        return self.flat.reconstruct_batch(ids, **kw)
+
+    def _refused(self, *a, **kw):
+        raise NotImplementedError("IvfIndex: the search over the probed lists is not in this build (DESIGN.md 4j); `flat` searches "
+                                  "the same rows exactly")
+
+    search = search_packed = search_wide = range_search = search_fused = search_wide_packed = _refused
+
+    # ------------------------------------------------------------------ persistence
+    #   the inner index's files (MipsIndex.save) + centroids.f32 (raw float32 [nlist, d]) + assign.i32 (int32 [ntotal]);
+    #   meta.json carries "nlist" and "niter"
+    def save(self, path: str, extra: dict | None = None) -> None:
+        if not self.is_trained:
+            raise RuntimeError("save: the IvfIndex is not trained")
+        ext = {"nlist": self._nlist, "niter": self._niter}
+        ext.update(extra or {})
+        MipsIndex.save(self.flat, path, extra=ext)
+        with open(os.path.join(path, "centroids.f32"), "wb") as f:
+            f.write(self.centroids().astype("<f4").tobytes())
+        with open(os.path.join(path, "assign.i32"), "wb") as f:
+            f.write(self.assignments().astype("<i4").tobytes())
+
+    @classmethod
+    def load(cls, path: str, device: int | None = None, chunk_rows: int = 1 << 16) -> "IvfIndex":
+        with open(os.path.join(path, "meta.json")) as f:
+            meta = json.load(f)
+        if meta.get("format") != _FORMAT_VERSION or "nlist" not in meta:
+            raise ValueError("not a saved IvfIndex")
+        n, d = meta["ntotal"], meta["d"]
+        ix = cls(d, meta["nlist"], dtype=meta["dtype"], device=device)
+        ix.niter = meta.get("niter", 10)
+        ix.set_centroids(np.fromfile(os.path.join(path, "centroids.f32"), dtype="<f4").reshape(ix.nlist, d))
+        if meta.get("sq8_vmin") is not None:
+            ix.set_sq8_params([float.fromhex(v) for v in meta["sq8_vmin"]], [float.fromhex(v) for v in meta["sq8_vdiff"]])
+        if n > 0:
+            fext, npdt = _ROWS_FILE[meta["dtype"]]
+            mm = np.memmap(os.path.join(path, "rows." + fext), dtype=npdt, mode="r", shape=(n, d))
+            for r0 in range(0, n, chunk_rows):  # the rows in their stored form, straight into the inner index
+                MipsIndex.add(ix.flat, np.asarray(mm[r0:min(n, r0 + chunk_rows)]))
+            del mm
+            assign = np.ascontiguousarray(np.fromfile(os.path.join(path, "assign.i32"), dtype="<i4").astype(np.int32))
+            with ix._mutex:
+                _lib.check(ix._lib.mips_ivf_set_assign(ix._h, assign.ctypes.data, n, _stream_handle(ix.device)), "mips_ivf_set_assign")
+            if meta.get("labels"):
+                ix.flat.set_labels(np.fromfile(os.path.join(path, "labels.i32"), dtype="<i4"))
+        ix.meta = meta
+        return ix
