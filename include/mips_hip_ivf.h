@@ -23,9 +23,15 @@
  *                    list_rows [ntotal], ascending inside each list) is rebuilt.  Rows are float32 or bf16 values: raw codes are
  *                    MIPS_E_UNSUPPORTED.
  *   probe(q, nprobe) P(q) = the p = min(nprobe, nlist) nearest lists of the float32 query, nearest first.
- * NOT IN THIS HEADER YET: the search over the probed lists (the flat index's mips_search restricted to the rows whose assignment
- * lies in P(q)).  What is here builds and maintains everything that search reads; until it exists, the rows are searched exactly
- * through mips_ivf_flat.
+ *   search(q, k, nprobe)  for query j: A_j = the rows i with assign_i in P(q_j); the result is what the flat index's mips_search
+ *                    returns for q_j on an index from which the rows outside A_j were deleted, row numbers kept: the flat storage's
+ *                    canonical score (bf16: stored bf16 rows, queries staged to bf16; F32: the caller's float32 rows and queries;
+ *                    SQ8: ranked by S(q, i), reported as D(q, i) = (float)((double)S + B_q) of mips_hip_sq8.h -- ranked and merged
+ *                    on S, converted to D once the order is fixed, so two rows with different S and equal D keep the order of S),
+ *                    order by (score descending, row ascending), -1 / -inf padding when |A_j| < k, idx_offset added to the rows.
+ *                    Hence: mips_score_subset on mips_ivf_flat of the returned rows gives the returned scores bit for bit, and
+ *                    nprobe >= nlist gives mips_search's result on mips_ivf_flat bit for bit.  Every row of the probed lists is
+ *                    scored exactly (the sequential fp64 sum); nothing is approximated and nothing needs a certificate.
  * Refused: MIPS_METRIC_L2 (the index ranks by inner product), d > 1024, the e4m3 storages, nlist outside 1 .. 65536, p > 1024.
  */
 #ifndef MIPS_HIP_IVF_H
@@ -60,8 +66,28 @@ int mips_ivf_add(mips_ivf_t* ivf, const void* rows, int64_t n, int src_dtype, in
 
 /* P(q): q [nq, d] float32 or bf16, host or device (MIPS_Q_DEVICE in flags); out_lists HOST int32 [nq, min(nprobe, nlist)], nearest
  * first.  nprobe >= 1, min(nprobe, nlist) <= 1024 (up to MIPS_MAX_K lists through mips_search, more through mips_search_wide: both
- * certified).  Synchronises. */
+ * certified).  Synchronises.  With MIPS_OUT_DEVICE in flags out_lists is DEVICE int32 [nq, p] and the call never synchronises (it
+ * writes through the scratch of mips_ivf_search and follows its capture contract, below). */
 int mips_ivf_probe(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int64_t nprobe, int32_t* out_lists, int flags, void* hip_stream);
+
+/* The search over the probed lists (the definition: "search" above).  q [nq, d] MIPS_DTYPE_F32 or MIPS_DTYPE_BF16, host or device
+ * (MIPS_Q_DEVICE); out_scores float32 / out_idx int64 [nq, k], host or device (MIPS_OUT_DEVICE); 1 <= k <= MIPS_MAX_K; nprobe as
+ * mips_ivf_probe.  Host outputs synchronise; a device-in / device-out call never does.
+ * MIPS_E_INVALID: an untrained index, a bad q_dtype, k outside 1 .. MIPS_MAX_K, nprobe < 1, NULL buffers with nq > 0.
+ * MIPS_E_UNSUPPORTED: min(nprobe, nlist) > 1024.  nq == 0: MIPS_OK, nothing written.  An empty index: padding (-1 / -inf).
+ * A query with a NaN or an infinity may get any result; it reads nothing outside the index.
+ *
+ * What a call enqueues is a fixed sequence -- the probe (the coarse index's own certified search), the staging of the queries as
+ * the flat index stages them, ONE list-scan launch of nq * p * S workgroups (S = segments per probed list, a power of two <= 32
+ * chosen from nq, p, k and the device's compute units), the merge of the sorted partial lists, a finishing pass over [nq, k] -- in
+ * which no grid, pointer, size or loop bound depends on the VALUES of the queries: list numbers, list bounds and row numbers are
+ * read and range-checked on the device.  Its scratch (probe buffer, staged queries, partial lists) is the search's own and grows
+ * only when a search asks for a larger (nq, p, S, k).  So in steady state a device-in / device-out search issues only stream
+ * operations and may be captured into a HIP graph and replayed with other queries; the captured graph stays valid until a search
+ * (or a device-output probe) of a larger shape, or until mips_ivf_train, _set_centroids, _add, _remove, _set_assign, _reset or
+ * _destroy (add also grows the coarse index's scratch and may move the rows and the list table). */
+int mips_ivf_search(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                    int64_t idx_offset, int flags, void* hip_stream);
 
 /* mips_index_remove on the inner index, the same order-preserving compaction of the assignments, the list table rebuilt.
  * Arguments as mips_index_remove (include/mips_hip_update.h); out_counts[0] = rows removed. */

@@ -2,7 +2,19 @@
 // two ordinary indexes -- `flat` holds the rows in arrival order, `coarse` (fp32-exact, inner product) holds the centroids and answers
 // every "nearest lists of x" through mips_search / mips_search_wide -- plus the rows' list numbers and the list table.  Device
 // resources are owned by type (DeviceArray, Buffer): `delete ivf` behind the two inner destroys leaves nothing.
+// mips_ivf_search (at the end) is a fixed launch sequence -- probe, stage, list scan, merge, finish -- in which every grid, pointer,
+// size and loop bound comes from (nq, p, k, d, nlist, the CU count) and the index object: nothing is read back from the device,
+// and everything that depends on the queries is read and range-checked by the kernels (ivf_search_kernels.hpp).
 #pragma once
+
+// What a search over the probed lists writes between its launches.  Its own: `cs` / `ci` below are resized by add and training,
+// these grow only when a search asks for a larger (nq, p, S, k) -- so a captured search stays valid across smaller ones.
+struct IvfSearchScratch {
+    Buffer ps, pi;            // the probe [ns][p]: scores, list numbers (int64)
+    Buffer qbuf, qf32, qbias; // staged queries as the flat index stages them (+ B_q of an SQ8 index)
+    Buffer parts;             // [p * S][ns][k][2] sorted partial lists
+    Buffer out_s, out_i;      // [nq][k] of a host-output call
+};
 
 struct mips_ivf {
     int device = 0;
@@ -21,6 +33,8 @@ struct mips_ivf {
     Buffer count;               // [nlist] histogram of a table build
     Buffer cs, ci;              // coarse results [nq][p]
     Buffer train_rows, train_assign, train_off, train_list, flag;
+    IvfSearchScratch ss;        // mips_ivf_search, and the device-output form of mips_ivf_probe
+    int cus = 1;                // compute units of the device (sizes the list scan)
     ~mips_ivf() {
         if (flat) (void)mips_index_destroy(flat);
         if (coarse) (void)mips_index_destroy(coarse);
@@ -114,15 +128,15 @@ int ivf_check(const char* who, const mips_ivf* v) {
     return MIPS_OK;
 }
 
-// P(q) of a query slice: ci [ns][p] on the device
-int ivf_probe_slice(mips_ivf* v, const void* q, int q_dtype, int64_t ns, int p, bool q_dev, hipStream_t st) {
-    int rc = v->cs.ensure((size_t)ns * p * sizeof(float));
+// P(q) of a query slice: ci [ns][p] on the device (cs / ci: the index's coarse results, or the search's own probe buffers)
+int ivf_probe_slice(mips_ivf* v, const void* q, int q_dtype, int64_t ns, int p, bool q_dev, Buffer& cs, Buffer& ci, hipStream_t st) {
+    int rc = cs.ensure((size_t)ns * p * sizeof(float));
     if (rc) return rc;
-    rc = v->ci.ensure((size_t)ns * p * sizeof(int64_t));
+    rc = ci.ensure((size_t)ns * p * sizeof(int64_t));
     if (rc) return rc;
     const int flags = (q_dev ? MIPS_Q_DEVICE : 0) | MIPS_OUT_DEVICE;
-    if (p <= MIPS_MAX_K) return mips_search(v->coarse, q, q_dtype, ns, p, (float*)v->cs.p, (int64_t*)v->ci.p, 0, flags, st);
-    return mips_search_wide(v->coarse, q, q_dtype, ns, p, (float*)v->cs.p, (int64_t*)v->ci.p, 0, flags, st);
+    if (p <= MIPS_MAX_K) return mips_search(v->coarse, q, q_dtype, ns, p, (float*)cs.p, (int64_t*)ci.p, 0, flags, st);
+    return mips_search_wide(v->coarse, q, q_dtype, ns, p, (float*)cs.p, (int64_t*)ci.p, 0, flags, st);
 }
 
 int ivf_query_args(const char* who, const mips_ivf* v, const void* q, int q_dtype, int64_t nq, int64_t nprobe, int* p) {
@@ -165,6 +179,7 @@ int mips_ivf_create(mips_ivf_t** out, int device, int64_t d, int doc_dtype, int 
     rc = mips_index_create(&v->coarse, device, d, MIPS_DTYPE_F32, MIPS_METRIC_IP);
     if (rc) return rc;
     DeviceGuard g(device);
+    HIP_TRY(hipDeviceGetAttribute(&v->cus, hipDeviceAttributeMultiprocessorCount, device));
     HIP_TRY(hipMalloc((void**)&v->cent.p, (size_t)nlist * d * sizeof(float)));
     HIP_TRY(hipMalloc((void**)&v->offsets.p, (size_t)(nlist + 1) * sizeof(int)));
     HIP_TRY(hipMemset(v->offsets.p, 0, (size_t)(nlist + 1) * sizeof(int)));
@@ -407,14 +422,108 @@ int mips_ivf_probe(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int64_
     DeviceGuard g(v->device);
     const hipStream_t st = (hipStream_t)hip_stream;
     const size_t esz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
+    if (flags & MIPS_OUT_DEVICE) { // into the search's probe buffer, then int32 to the caller: stream operations only
+        for (int64_t s0 = 0; s0 < nq; s0 += 4096) {
+            const int64_t ns = std::min<int64_t>(4096, nq - s0);
+            if ((rc = ivf_probe_slice(v, (const char*)q + (size_t)s0 * v->d * esz, q_dtype, ns, p, (flags & MIPS_Q_DEVICE) != 0, v->ss.ps, v->ss.pi, st)))
+                return rc;
+            mips::ivf_to_assign_kernel<<<grid_for(ns * p, 256), 256, 0, st>>>((const int64_t*)v->ss.pi.p, ns * p, v->nlist, out_lists + (size_t)s0 * p);
+            HIP_TRY(hipGetLastError());
+        }
+        return MIPS_OK;
+    }
     std::vector<int64_t> h;
     for (int64_t s0 = 0; s0 < nq; s0 += 4096) {
         const int64_t ns = std::min<int64_t>(4096, nq - s0);
-        if ((rc = ivf_probe_slice(v, (const char*)q + (size_t)s0 * v->d * esz, q_dtype, ns, p, (flags & MIPS_Q_DEVICE) != 0, st))) return rc;
+        if ((rc = ivf_probe_slice(v, (const char*)q + (size_t)s0 * v->d * esz, q_dtype, ns, p, (flags & MIPS_Q_DEVICE) != 0, v->cs, v->ci, st))) return rc;
         h.resize((size_t)ns * p);
         HIP_TRY(hipMemcpyAsync(h.data(), v->ci.p, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         for (size_t t = 0; t < h.size(); ++t) out_lists[(size_t)s0 * p + t] = (int32_t)h[t];
+    }
+    return MIPS_OK;
+}
+
+int mips_ivf_search(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx, int64_t idx_offset,
+                    int flags, void* hip_stream) {
+    int rc = ivf_check("mips_ivf_search", v);
+    if (rc) return rc;
+    if (mips_ivf_is_trained(v) != 1) return fail(MIPS_E_INVALID, "mips_ivf_search: the IVF index is not trained (mips_ivf_train / mips_ivf_set_centroids)");
+    int p = 0;
+    if ((rc = ivf_query_args("mips_ivf_search", v, q, q_dtype, nq, nprobe, &p))) return rc;
+    if (k < 1 || k > MIPS_MAX_K) return fail(MIPS_E_INVALID, "mips_ivf_search: k must be 1 .. %d, got %d", MIPS_MAX_K, k);
+    if (nq == 0) return MIPS_OK;
+    if (!out_scores || !out_idx) return fail(MIPS_E_INVALID, "mips_ivf_search: NULL buffer");
+    mips_index* ix = v->flat;
+    const bool q_dev = (flags & MIPS_Q_DEVICE) != 0, out_dev = (flags & MIPS_OUT_DEVICE) != 0;
+    const bool f32x = ix->plane > 0;
+    const int ld = f32x ? ix->plane : ix->ld; // elements per canonical row and per staged query
+    const int per16 = f32x ? 4 : ix->esize == 2 ? 8 : 16;
+    if (ld > mips::IVF_SCAN_MAX_LD || ld % (per16 * mips::IVF_SCAN_TCH) != 0)
+        return fail(MIPS_E_UNSUPPORTED, "mips_ivf_search: row pitch %d is not served", ld);
+    DeviceGuard g(v->device);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st); // (the staging below is the flat index's; the coarse index orders its own calls)
+    IvfSearchScratch& ss = v->ss;
+    float* d_s = out_scores;
+    int64_t* d_i = out_idx;
+    if (!out_dev) {
+        if ((rc = ss.out_s.ensure((size_t)nq * k * sizeof(float)))) return rc;
+        if ((rc = ss.out_i.ensure((size_t)nq * k * sizeof(int64_t)))) return rc;
+        d_s = (float*)ss.out_s.p;
+        d_i = (int64_t*)ss.out_i.p;
+    }
+    const size_t esz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
+    const int64_t slice = ivf::slice_queries(p, k);
+    for (int64_t s0 = 0; s0 < nq; s0 += slice) {
+        const int64_t ns = std::min(slice, nq - s0);
+        const void* qs = (const char*)q + (size_t)s0 * v->d * esz;
+        const int S = ivf::choose_segments(ns, p, k, v->cus);
+        // 1. the probe: the coarse index's own certified search, into the search's buffer
+        if ((rc = ivf_probe_slice(v, qs, q_dtype, ns, p, q_dev, ss.ps, ss.pi, st))) return rc;
+        // 2. the queries, staged as the flat index stages them for its storage
+        if ((rc = ss.qbuf.ensure((size_t)ns * ix->ld * ix->qsize))) return rc;
+        if (f32x) {
+            if ((rc = ss.qf32.ensure((size_t)ns * ix->plane * sizeof(float)))) return rc;
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, (float*)ss.qf32.p);
+        } else {
+            if (ix->sq8 && (rc = ss.qbias.ensure((size_t)ns * sizeof(double)))) return rc;
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize, (double*)ss.qbias.p);
+        }
+        if (rc) return rc;
+        // 3. the list scan: one workgroup per (query, probed list, segment)
+        const int parts = p * S;
+        if ((rc = ss.parts.ensure((size_t)parts * ns * k * 2 * sizeof(int64_t)))) return rc;
+        mips::IvfScanArgs a;
+        a.rows = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
+        a.y = f32x ? ss.qf32.p : ss.qbuf.p;
+        a.ld = ld;
+        a.ntotal = ix->ntotal;
+        a.probe = (const int64_t*)ss.pi.p;
+        a.offsets = v->offsets;
+        a.list_rows = v->list_rows;
+        a.nlist = v->nlist;
+        a.nq = ns;
+        a.p = p;
+        a.S = S;
+        a.k = k;
+        a.parts = (int64_t*)ss.parts.p;
+        const unsigned grid = (unsigned)(ns * parts); // <= 4096 * 1024, or < 2 * cus * 32
+        constexpr int threads = 64 * mips::IVF_SCAN_WAVES;
+        if (f32x) mips::ivf_list_scan_kernel<mips::ElemF32, mips::ElemF32><<<grid, threads, 0, st>>>(a);
+        else if (ix->sq8) mips::ivf_list_scan_kernel<mips::ElemU8, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
+        else mips::ivf_list_scan_kernel<mips::ElemBF16, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
+        HIP_TRY(hipGetLastError());
+        // 4. the merge of the sorted partials (score descending, row ascending, padding last), then S -> D and idx_offset
+        if ((rc = mips_merge_topk_sorted_packed(a.parts, ns, parts, k, MIPS_METRIC_IP, d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, v->device, st))) return rc;
+        mips::ivf_finish_kernel<<<grid_for(ns * k, 256), 256, 0, st>>>(d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, ix->sq8 ? (const double*)ss.qbias.p : nullptr, ns,
+                                                                      k, idx_offset);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!out_dev) {
+        HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
     }
     return MIPS_OK;
 }

@@ -7,7 +7,7 @@
 //   training       ivf_gather_rows_kernel (the training set as float32), ivf_finite_kernel, ivf_init_centroids_kernel,
 //                  ivf_centroid_sum_kernel (one thread per (list, column): sequential fp64 sum of the members in ascending row
 //                  order), ivf_normalise_kernel (one thread per list).  The arithmetic is csrc/ivf_math.hpp.
-// The scan of the probed lists is not part of this file yet (DESIGN.md section 4j says why).
+// The scan of the probed lists: ivf_search_kernels.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

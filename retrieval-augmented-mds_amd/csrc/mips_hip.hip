@@ -42,6 +42,7 @@
 #include "sq8_kernels.hpp"
 #include "sq8_scan_kernel.hpp"
 #include "ivf_kernels.hpp"
+#include "ivf_search_kernels.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"

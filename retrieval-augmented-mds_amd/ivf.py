@@ -1,8 +1,9 @@
 """IvfIndex -- an inverted file (k-means lists, nprobe) over the rows of a flat index (include/mips_hip_ivf.h).
 
-What is here builds and maintains the file: deterministic k-means training, the list of every added row, the list table, the
-probed lists P(q) of a query, removal, reset, save / load.  The search over the probed lists is NOT in this build yet (DESIGN.md
-4j); `flat` is the inner MipsIndex over the same rows and searches them exactly.
+Building and maintaining the file: deterministic k-means training, the list of every added row, the list table, the probed lists
+P(q) of a query, removal, reset, save / load.  Searching it: `search_probed` scores every row of the probed lists exactly and
+returns what `flat.search` would return if the other rows were deleted; `flat` is the inner MipsIndex over the same rows and
+searches all of them.
 
 All arithmetic happens in libmips_hip.so; this file moves pointers.  No CPU fallback.
 """
@@ -192,18 +193,54 @@ class IvfIndex:
         return out
 
     # ------------------------------------------------------------------ searching
-    def probe(self, x, nprobe: int | None = None) -> np.ndarray:
-        """P(q): int32 [nq, min(nprobe, nlist)], the probed lists of every query, nearest first."""
+    def probe(self, x, nprobe: int | None = None, device_out: bool = False):
+        """P(q): int32 [nq, min(nprobe, nlist)], the probed lists of every query, nearest first.  A NumPy array; with device_out
+        (CUDA queries only) a CUDA tensor, stream-ordered: nothing synchronises, so the call may be captured into a graph."""
         nprobe = int(self.nprobe if nprobe is None else nprobe)
         ptr, code, is_dev, nq, keep = self._rows(x, "probe")
         if nprobe < 1:
             raise ValueError("nprobe must be >= 1")
+        if device_out:
+            import torch
+
+            if not is_dev:
+                raise ValueError("probe(device_out=True) takes CUDA queries")
+            out = torch.empty((nq, min(nprobe, self._nlist)), dtype=torch.int32, device=f"cuda:{self.device}")
+            with self._mutex:
+                _lib.check(self._lib.mips_ivf_probe(self._h, ptr, code, nq, nprobe, out.data_ptr(), _lib.Q_DEVICE | _lib.OUT_DEVICE,
+                                                    _stream_handle(self.device)), "mips_ivf_probe")
+            del keep
+            return out
         out = np.empty((nq, min(nprobe, self._nlist)), np.int32)
         with self._mutex:
             _lib.check(self._lib.mips_ivf_probe(self._h, ptr, code, nq, nprobe, out.ctypes.data, _lib.Q_DEVICE if is_dev else 0,
                                                 _stream_handle(self.device)), "mips_ivf_probe")
         del keep
         return out
+
+    def search_probed(self, x, k: int, nprobe: int | None = None, idx_offset: int = 0):
+        """(D, I) [nq, k]: for every query the best k of the rows whose list lies in P(q) -- the flat storage's canonical score, ordered
+        by (score descending, row ascending), -1 / -inf padding (include/mips_hip_ivf.h).  nprobe defaults to self.nprobe.  NumPy in
+        gives NumPy out; a CUDA tensor in gives CUDA tensors out, stream-ordered (graph-capturable in steady state)."""
+        nprobe = int(self.nprobe if nprobe is None else nprobe)
+        k = int(k)
+        ptr, code, is_dev, nq, keep = self._rows(x, "search_probed")
+        stream = _stream_handle(self.device)
+        if is_dev:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            D = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+            I = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+            dp, ip, flags = D.data_ptr(), I.data_ptr(), _lib.Q_DEVICE | _lib.OUT_DEVICE
+        else:
+            D = np.empty((nq, max(k, 0)), np.float32)
+            I = np.empty((nq, max(k, 0)), np.int64)
+            dp, ip, flags = D.ctypes.data, I.ctypes.data, 0
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_search(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags, stream), "mips_ivf_search")
+        del keep
+        return D, I
 
     # rows by id: the inner flat index's (row ids are the flat ids)
     def reconstruct(self, key: int):
@@ -216,8 +253,8 @@ class IvfIndex:
         return self.flat.reconstruct_batch(ids, **kw)
 
     def _refused(self, *a, **kw):
-        raise NotImplementedError("IvfIndex: the search over the probed lists is not in this build (DESIGN.md 4j); `flat` searches "
-                                  "the same rows exactly")
+        raise NotImplementedError("IvfIndex: the search over the probed lists is search_probed(x, k, nprobe) (DESIGN.md 4j); the faiss-shaped "
+                                  "forms are not served on an IVF index, and `flat` searches all rows exactly")
 
     search = search_packed = search_wide = range_search = search_fused = search_wide_packed = _refused
 
