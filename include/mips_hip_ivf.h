@@ -89,6 +89,36 @@ int mips_ivf_probe(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int6
 int mips_ivf_search(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
                     int64_t idx_offset, int flags, void* hip_stream);
 
+/* The search over the probed lists under a filter: a bitmap over the rows (_sel), and per-query group labels on top of it (_grp).
+ * Row i is ADMITTED for query j iff both hold:
+ *   - sel_bits == NULL, or bit sel_bit0 + i of the bitmap is set (least significant bit of a byte first);
+ *   - q_labels == NULL, or the group rule holds: q_labels[j] == MIPS_LABEL_NONE, or label[i] != q_labels[j] under
+ *     MIPS_GRP_EXCLUDE, or label[i] == q_labels[j] under MIPS_GRP_ONLY.
+ * Layout, flags (MIPS_SEL_DEVICE: sel_bits is device memory; MIPS_GRP_DEVICE: q_labels [nq] is device memory) and labels are those
+ * of mips_search_wide_sel / _grp (mips_hip.h); label[i] is the label of the inner flat index (mips_index_set_labels on
+ * mips_ivf_flat), which follows its row through mips_ivf_remove.
+ * The result for query j is what mips_ivf_search returns for j on an index from which the rows not admitted for j were deleted,
+ * row numbers kept: the best k of A_j n admitted_j by the storage's canonical score (SQ8 ranked and merged on S, turned into D once
+ * the order is fixed), order (score descending, row ascending), -1 / -inf padding, idx_offset added.  Everything stays exact.
+ * Hence: with sel_bits == NULL and q_labels == NULL the call IS mips_ivf_search (same launches, same bits); on a BF16 or F32 index
+ * with nprobe >= nlist the result is the first k columns of mips_search_wide_grp(k = 30) under the same filter, bit for bit; and
+ * mips_score_subset on mips_ivf_flat reproduces the scores.  A filtered top-k cannot be had by fetching more and dropping: a group
+ * has no bounded size.  The rule is applied inside the list scan, where a row number is read; the bytes of a row that is not
+ * admitted are never requested, and the admitted rows are compacted before they are scored, so a sparse filter costs what it admits.
+ * mips_ivf_search_sel is mips_ivf_search_grp with q_labels == NULL.
+ * MIPS_E_INVALID: what mips_ivf_search refuses; sel_bit0 < 0 or sel_bit0 + ntotal > sel_nbits; a grp_mode other than 0 / 1; a
+ * grouped call on an index whose labelled prefix is not exactly ntotal.  nq == 0: MIPS_OK.  Limits: those of mips_ivf_search.
+ * A host bitmap (the bytes that cover the index's rows) and host q_labels travel by the stream's asynchronous copy into the
+ * search's own scratch.  With device queries, outputs, bitmap and labels the call issues only stream operations, and no grid,
+ * pointer, size or loop bound depends on the VALUES of the queries, the query labels or the bitmap: the capture contract of
+ * mips_ivf_search holds, and a captured graph replays with other queries, other q_labels contents and other bitmap contents of
+ * the same size. */
+int mips_ivf_search_sel(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                        int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream);
+int mips_ivf_search_grp(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                        int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels,
+                        int grp_mode, void* hip_stream);
+
 /* mips_index_remove on the inner index, the same order-preserving compaction of the assignments, the list table rebuilt.
  * Arguments as mips_index_remove (include/mips_hip_update.h); out_counts[0] = rows removed. */
 int mips_ivf_remove(mips_ivf_t* ivf, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, int flags, int64_t out_counts[2],

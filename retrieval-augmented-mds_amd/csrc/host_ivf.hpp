@@ -14,6 +14,7 @@ struct IvfSearchScratch {
     Buffer qbuf, qf32, qbias; // staged queries as the flat index stages them (+ B_q of an SQ8 index)
     Buffer parts;             // [p * S][ns][k][2] sorted partial lists
     Buffer out_s, out_i;      // [nq][k] of a host-output call
+    Buffer sel, qlab;         // a host bitmap and host query labels of a filtered call (mips_ivf_search_sel / _grp)
 };
 
 struct mips_ivf {
@@ -148,6 +149,122 @@ int ivf_query_args(const char* who, const mips_ivf* v, const void* q, int q_dtyp
     const int64_t pp = std::min<int64_t>(nprobe, v->nlist);
     if (pp > mips::IVF_MAX_PROBE) return fail(MIPS_E_UNSUPPORTED, "%s: min(nprobe, nlist) = %lld exceeds %d", who, (long long)pp, mips::IVF_MAX_PROBE);
     *p = (int)pp;
+    return MIPS_OK;
+}
+
+// mips_ivf_search (sel_bits == nullptr and q_labels == nullptr: the unfiltered launch sequence, nothing else is touched) and
+// mips_ivf_search_sel / _grp: the same sequence with the filtered instance of the list scan
+int ivf_search_impl(const char* who, mips_ivf* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                    int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels, int grp_mode,
+                    void* hip_stream) {
+    int rc = ivf_check(who, v);
+    if (rc) return rc;
+    if (mips_ivf_is_trained(v) != 1) return fail(MIPS_E_INVALID, "%s: the IVF index is not trained (mips_ivf_train / mips_ivf_set_centroids)", who);
+    int p = 0;
+    if ((rc = ivf_query_args(who, v, q, q_dtype, nq, nprobe, &p))) return rc;
+    if (k < 1 || k > MIPS_MAX_K) return fail(MIPS_E_INVALID, "%s: k must be 1 .. %d, got %d", who, MIPS_MAX_K, k);
+    mips_index* ix = v->flat;
+    const bool filtered = sel_bits != nullptr || q_labels != nullptr;
+    Selector sel;
+    if (filtered && (rc = make_selector(who, ix, flags, sel_bits, sel_nbits, sel_bit0, q_labels, grp_mode, sel))) return rc;
+    if (nq == 0) return MIPS_OK;
+    if (!out_scores || !out_idx) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
+    const bool q_dev = (flags & MIPS_Q_DEVICE) != 0, out_dev = (flags & MIPS_OUT_DEVICE) != 0;
+    const bool f32x = ix->plane > 0;
+    const int ld = f32x ? ix->plane : ix->ld; // elements per canonical row and per staged query
+    const int per16 = f32x ? 4 : ix->esize == 2 ? 8 : 16;
+    if (ld > mips::IVF_SCAN_MAX_LD || ld % (per16 * mips::IVF_SCAN_TCH) != 0)
+        return fail(MIPS_E_UNSUPPORTED, "%s: row pitch %d is not served", who, ld);
+    DeviceGuard g(v->device);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st); // (the staging below is the flat index's; the coarse index orders its own calls)
+    IvfSearchScratch& ss = v->ss;
+    float* d_s = out_scores;
+    int64_t* d_i = out_idx;
+    if (!out_dev) {
+        if ((rc = ss.out_s.ensure((size_t)nq * k * sizeof(float)))) return rc;
+        if ((rc = ss.out_i.ensure((size_t)nq * k * sizeof(int64_t)))) return rc;
+        d_s = (float*)ss.out_s.p;
+        d_i = (int64_t*)ss.out_i.p;
+    }
+    // a host bitmap (the bytes that hold bits sel_bit0 .. sel_bit0 + ntotal - 1) and host query labels travel by the stream's
+    // asynchronous copy into the search's scratch; device ones are read where they are
+    const uint8_t* d_bits = sel_bits;
+    int64_t d_bit0 = sel_bit0;
+    const int* d_qlab = (const int*)q_labels;
+    if (sel_bits && !sel.dev && ix->ntotal > 0) {
+        const int64_t b0 = sel_bit0 >> 3, b1 = (sel_bit0 + ix->ntotal + 7) >> 3;
+        if ((rc = ss.sel.ensure((size_t)(b1 - b0)))) return rc;
+        HIP_TRY(hipMemcpyAsync(ss.sel.p, sel_bits + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, st));
+        d_bits = (const uint8_t*)ss.sel.p;
+        d_bit0 = sel_bit0 & 7;
+    }
+    if (q_labels && !sel.qlab_dev) {
+        if ((rc = ss.qlab.ensure((size_t)nq * sizeof(int)))) return rc;
+        HIP_TRY(hipMemcpyAsync(ss.qlab.p, q_labels, (size_t)nq * sizeof(int), hipMemcpyHostToDevice, st));
+        d_qlab = (const int*)ss.qlab.p;
+    }
+    const size_t esz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
+    const int64_t slice = ivf::slice_queries(p, k);
+    for (int64_t s0 = 0; s0 < nq; s0 += slice) {
+        const int64_t ns = std::min(slice, nq - s0);
+        const void* qs = (const char*)q + (size_t)s0 * v->d * esz;
+        const int S = ivf::choose_segments(ns, p, k, v->cus);
+        // 1. the probe: the coarse index's own certified search, into the search's buffer
+        if ((rc = ivf_probe_slice(v, qs, q_dtype, ns, p, q_dev, ss.ps, ss.pi, st))) return rc;
+        // 2. the queries, staged as the flat index stages them for its storage
+        if ((rc = ss.qbuf.ensure((size_t)ns * ix->ld * ix->qsize))) return rc;
+        if (f32x) {
+            if ((rc = ss.qf32.ensure((size_t)ns * ix->plane * sizeof(float)))) return rc;
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, (float*)ss.qf32.p);
+        } else {
+            if (ix->sq8 && (rc = ss.qbias.ensure((size_t)ns * sizeof(double)))) return rc;
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize, (double*)ss.qbias.p);
+        }
+        if (rc) return rc;
+        // 3. the list scan: one workgroup per (query, probed list, segment)
+        const int parts = p * S;
+        if ((rc = ss.parts.ensure((size_t)parts * ns * k * 2 * sizeof(int64_t)))) return rc;
+        mips::IvfScanArgs a;
+        a.rows = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
+        a.y = f32x ? ss.qf32.p : ss.qbuf.p;
+        a.ld = ld;
+        a.ntotal = ix->ntotal;
+        a.probe = (const int64_t*)ss.pi.p;
+        a.offsets = v->offsets;
+        a.list_rows = v->list_rows;
+        a.nlist = v->nlist;
+        a.nq = ns;
+        a.p = p;
+        a.S = S;
+        a.k = k;
+        a.parts = (int64_t*)ss.parts.p;
+        a.sel_bits = d_bits;
+        a.sel_bit0 = d_bit0;
+        a.row_labels = ix->labels;
+        a.q_labels = d_qlab ? d_qlab + s0 : nullptr;
+        a.grp_mode = sel.grp_only ? MIPS_GRP_ONLY : MIPS_GRP_EXCLUDE;
+        const unsigned grid = (unsigned)(ns * parts); // <= 4096 * 1024, or < 2 * cus * 32
+        constexpr int threads = 64 * mips::IVF_SCAN_WAVES;
+        if (filtered) {
+            if (f32x) mips::ivf_list_scan_kernel<mips::ElemF32, mips::ElemF32, true><<<grid, threads, 0, st>>>(a);
+            else if (ix->sq8) mips::ivf_list_scan_kernel<mips::ElemU8, mips::ElemBF16, true><<<grid, threads, 0, st>>>(a);
+            else mips::ivf_list_scan_kernel<mips::ElemBF16, mips::ElemBF16, true><<<grid, threads, 0, st>>>(a);
+        } else if (f32x) mips::ivf_list_scan_kernel<mips::ElemF32, mips::ElemF32><<<grid, threads, 0, st>>>(a);
+        else if (ix->sq8) mips::ivf_list_scan_kernel<mips::ElemU8, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
+        else mips::ivf_list_scan_kernel<mips::ElemBF16, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
+        HIP_TRY(hipGetLastError());
+        // 4. the merge of the sorted partials (score descending, row ascending, padding last), then S -> D and idx_offset
+        if ((rc = mips_merge_topk_sorted_packed(a.parts, ns, parts, k, MIPS_METRIC_IP, d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, v->device, st))) return rc;
+        mips::ivf_finish_kernel<<<grid_for(ns * k, 256), 256, 0, st>>>(d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, ix->sq8 ? (const double*)ss.qbias.p : nullptr, ns,
+                                                                      k, idx_offset);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!out_dev) {
+        HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
     return MIPS_OK;
 }
 
@@ -446,86 +563,20 @@ int mips_ivf_probe(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int64_
 
 int mips_ivf_search(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx, int64_t idx_offset,
                     int flags, void* hip_stream) {
-    int rc = ivf_check("mips_ivf_search", v);
-    if (rc) return rc;
-    if (mips_ivf_is_trained(v) != 1) return fail(MIPS_E_INVALID, "mips_ivf_search: the IVF index is not trained (mips_ivf_train / mips_ivf_set_centroids)");
-    int p = 0;
-    if ((rc = ivf_query_args("mips_ivf_search", v, q, q_dtype, nq, nprobe, &p))) return rc;
-    if (k < 1 || k > MIPS_MAX_K) return fail(MIPS_E_INVALID, "mips_ivf_search: k must be 1 .. %d, got %d", MIPS_MAX_K, k);
-    if (nq == 0) return MIPS_OK;
-    if (!out_scores || !out_idx) return fail(MIPS_E_INVALID, "mips_ivf_search: NULL buffer");
-    mips_index* ix = v->flat;
-    const bool q_dev = (flags & MIPS_Q_DEVICE) != 0, out_dev = (flags & MIPS_OUT_DEVICE) != 0;
-    const bool f32x = ix->plane > 0;
-    const int ld = f32x ? ix->plane : ix->ld; // elements per canonical row and per staged query
-    const int per16 = f32x ? 4 : ix->esize == 2 ? 8 : 16;
-    if (ld > mips::IVF_SCAN_MAX_LD || ld % (per16 * mips::IVF_SCAN_TCH) != 0)
-        return fail(MIPS_E_UNSUPPORTED, "mips_ivf_search: row pitch %d is not served", ld);
-    DeviceGuard g(v->device);
-    const hipStream_t st = (hipStream_t)hip_stream;
-    ORDER_ON(ix, st); // (the staging below is the flat index's; the coarse index orders its own calls)
-    IvfSearchScratch& ss = v->ss;
-    float* d_s = out_scores;
-    int64_t* d_i = out_idx;
-    if (!out_dev) {
-        if ((rc = ss.out_s.ensure((size_t)nq * k * sizeof(float)))) return rc;
-        if ((rc = ss.out_i.ensure((size_t)nq * k * sizeof(int64_t)))) return rc;
-        d_s = (float*)ss.out_s.p;
-        d_i = (int64_t*)ss.out_i.p;
-    }
-    const size_t esz = q_dtype == MIPS_DTYPE_F32 ? 4 : 2;
-    const int64_t slice = ivf::slice_queries(p, k);
-    for (int64_t s0 = 0; s0 < nq; s0 += slice) {
-        const int64_t ns = std::min(slice, nq - s0);
-        const void* qs = (const char*)q + (size_t)s0 * v->d * esz;
-        const int S = ivf::choose_segments(ns, p, k, v->cus);
-        // 1. the probe: the coarse index's own certified search, into the search's buffer
-        if ((rc = ivf_probe_slice(v, qs, q_dtype, ns, p, q_dev, ss.ps, ss.pi, st))) return rc;
-        // 2. the queries, staged as the flat index stages them for its storage
-        if ((rc = ss.qbuf.ensure((size_t)ns * ix->ld * ix->qsize))) return rc;
-        if (f32x) {
-            if ((rc = ss.qf32.ensure((size_t)ns * ix->plane * sizeof(float)))) return rc;
-            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, (float*)ss.qf32.p);
-        } else {
-            if (ix->sq8 && (rc = ss.qbias.ensure((size_t)ns * sizeof(double)))) return rc;
-            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize, (double*)ss.qbias.p);
-        }
-        if (rc) return rc;
-        // 3. the list scan: one workgroup per (query, probed list, segment)
-        const int parts = p * S;
-        if ((rc = ss.parts.ensure((size_t)parts * ns * k * 2 * sizeof(int64_t)))) return rc;
-        mips::IvfScanArgs a;
-        a.rows = f32x ? (const void*)ix->rows_f32.p : (const void*)ix->rows.p;
-        a.y = f32x ? ss.qf32.p : ss.qbuf.p;
-        a.ld = ld;
-        a.ntotal = ix->ntotal;
-        a.probe = (const int64_t*)ss.pi.p;
-        a.offsets = v->offsets;
-        a.list_rows = v->list_rows;
-        a.nlist = v->nlist;
-        a.nq = ns;
-        a.p = p;
-        a.S = S;
-        a.k = k;
-        a.parts = (int64_t*)ss.parts.p;
-        const unsigned grid = (unsigned)(ns * parts); // <= 4096 * 1024, or < 2 * cus * 32
-        constexpr int threads = 64 * mips::IVF_SCAN_WAVES;
-        if (f32x) mips::ivf_list_scan_kernel<mips::ElemF32, mips::ElemF32><<<grid, threads, 0, st>>>(a);
-        else if (ix->sq8) mips::ivf_list_scan_kernel<mips::ElemU8, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
-        else mips::ivf_list_scan_kernel<mips::ElemBF16, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
-        HIP_TRY(hipGetLastError());
-        // 4. the merge of the sorted partials (score descending, row ascending, padding last), then S -> D and idx_offset
-        if ((rc = mips_merge_topk_sorted_packed(a.parts, ns, parts, k, MIPS_METRIC_IP, d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, v->device, st))) return rc;
-        mips::ivf_finish_kernel<<<grid_for(ns * k, 256), 256, 0, st>>>(d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, ix->sq8 ? (const double*)ss.qbias.p : nullptr, ns,
-                                                                      k, idx_offset);
-        HIP_TRY(hipGetLastError());
-    }
-    if (!out_dev) {
-        HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out_idx, d_i, (size_t)nq * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    return MIPS_OK;
+    return ivf_search_impl("mips_ivf_search", v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, nullptr, 0, 0, nullptr, 0, hip_stream);
+}
+
+int mips_ivf_search_sel(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                        int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
+    return ivf_search_impl("mips_ivf_search_sel", v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, sel_bits, sel_nbits, sel_bit0, nullptr,
+                           0, hip_stream);
+}
+
+int mips_ivf_search_grp(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                        int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels, int grp_mode,
+                        void* hip_stream) {
+    return ivf_search_impl(q_labels ? "mips_ivf_search_grp" : "mips_ivf_search_sel", v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags,
+                           sel_bits, sel_nbits, sel_bit0, q_labels, grp_mode, hip_stream);
 }
 
 } // extern "C"

@@ -12,6 +12,12 @@
 //                          resolve_overflow_kernel); the waves' lists meet in LDS and wave 0 writes the workgroup's sorted partial
 //                          of k entries, padding (-inf, -1) last, in the MIPS_OUT_PACKED layout [p * S][nq][k][2] that
 //                          merge_topk_sorted_packed_kernel reads.
+//                          FILT (mips_ivf_search_sel / _grp): the lane that reads a row number also reads the row's bit and label
+//                          and drops a row that is not admitted there, before any of its bytes is requested; the admitted row
+//                          numbers are compacted through a per-wave queue in LDS (ivf_filter_math.hpp) and scored 64 at a time,
+//                          so a sparse filter costs passes for the rows it admits, not for the positions it walks.  The order
+//                          (key descending, row ascending) is total, so the order in which rows are scored does not show in the
+//                          result.  FILT = false compiles the unfiltered kernel: no queue, no extra LDS, the same registers.
 //   ivf_finish_kernel      behind the merge, over [nq][k]: SQ8 scores S -> D = (float)((double)S + B_q) (sq8_bias_kernel's
 //                          arithmetic), idx_offset added to the rows; padding stays (-inf, -1).
 #pragma once
@@ -19,6 +25,7 @@
 #include <stdint.h>
 
 #include "aux_kernels.hpp"
+#include "ivf_filter_math.hpp"
 #include "ivf_search_math.hpp"
 
 namespace mips {
@@ -40,6 +47,12 @@ struct IvfScanArgs {
     int64_t nq;
     int p, S, k;
     int64_t* parts;         // [p * S][nq][k][2]
+    // the filtered instances only (FILT); a null pointer switches that half of the rule off
+    const uint8_t* sel_bits; // bit sel_bit0 + i decides row i
+    int64_t sel_bit0;
+    const int* row_labels;   // [ntotal] the flat index's labels
+    const int* q_labels;     // [nq]
+    int grp_mode;            // MIPS_GRP_EXCLUDE / MIPS_GRP_ONLY
 };
 
 // The canonical dot product of row `id` of this lane (id < 0: no row; the lane reads row 0 and the caller drops the result) with
@@ -81,13 +94,45 @@ __device__ __forceinline__ double ivf_gathered_dot(const typename EL::type* rows
     return acc;
 }
 
-// EL: element type of the rows; ELQ: of the staged queries (bf16 for SQ8 codes)
-template <typename EL, typename ELQ>
+// One scoring pass: lane `lane` scores row `id` (id < 0: none) and the wave inserts what ranks among its best K into its sorted list
+// (lk, li, cnt): lane u < cnt holds the wave's u-th best by (key descending, row ascending).
+template <typename EL>
+__device__ __forceinline__ void ivf_score_insert(const typename EL::type* rows, int ld, int id, int lane, u32x4* tile, const double* yd, int K, float& lk,
+                                                 int& li, int& cnt) {
+    const float key = (float)ivf_gathered_dot<EL>(rows, ld, id, lane, tile, yd);
+    const float wk = __shfl(lk, K - 1);
+    const int wi = __shfl(li, K - 1);
+    unsigned long long m = __ballot(id >= 0 && (cnt < K || ranks_before(key, id, wk, wi)));
+    while (m != 0ull) { // one candidate at a time, the whole wave on it
+        const int c = __ffsll((long long)m) - 1;
+        m &= m - 1ull;
+        const float nk = __shfl(key, c);
+        const int ni = __shfl(id, c);
+        const int at = __popcll(__ballot(lane < cnt && ranks_before(lk, li, nk, ni)));
+        if (at < K) {
+            const int from = lane > 0 ? lane - 1 : 0;
+            const float uk = __shfl(lk, from);
+            const int ui = __shfl(li, from);
+            if (lane > at) {
+                lk = uk;
+                li = ui;
+            } else if (lane == at) {
+                lk = nk;
+                li = ni;
+            }
+            cnt = cnt < K ? cnt + 1 : K;
+        }
+    }
+}
+
+// EL: element type of the rows; ELQ: of the staged queries (bf16 for SQ8 codes); FILT: the filtered instance
+template <typename EL, typename ELQ, bool FILT = false>
 __global__ __launch_bounds__(64 * IVF_SCAN_WAVES) void ivf_list_scan_kernel(IvfScanArgs a) {
     __shared__ __attribute__((aligned(16))) double yd[IVF_SCAN_MAX_LD];
     __shared__ __attribute__((aligned(16))) u32x4 tiles[IVF_SCAN_WAVES * 64 * (IVF_SCAN_TCH + 1)];
     __shared__ float mk[IVF_SCAN_WAVES * IVF_SCAN_KSLOT];
     __shared__ int mi[IVF_SCAN_WAVES * IVF_SCAN_KSLOT];
+    __shared__ int fq[FILT ? IVF_SCAN_WAVES * ivf::kQueueSlots : 1]; // the waves' queues of admitted row numbers
     __shared__ int mc[IVF_SCAN_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int K = a.k;
@@ -122,6 +167,9 @@ __global__ __launch_bounds__(64 * IVF_SCAN_WAVES) void ivf_list_scan_kernel(IvfS
         __syncthreads();
         const typename EL::type* rows = reinterpret_cast<const typename EL::type*>(a.rows);
         u32x4* tile = tiles + wave * 64 * (IVF_SCAN_TCH + 1);
+        int* queue = fq + (FILT ? wave * ivf::kQueueSlots : 0);
+        int queued = 0; // entries of the wave's queue, < 64 between windows
+        const int qlab = FILT && a.q_labels != nullptr ? a.q_labels[j] : ivf::kLabelNone;
         for (int64_t r0 = lo + (int64_t)wave * 64; r0 < hi; r0 += 64 * IVF_SCAN_WAVES) {
             const int64_t pos = r0 + lane;
             int id = -1;
@@ -129,30 +177,29 @@ __global__ __launch_bounds__(64 * IVF_SCAN_WAVES) void ivf_list_scan_kernel(IvfS
                 const int r = a.list_rows[pos];
                 if (r >= 0 && r < a.ntotal) id = r;
             }
-            const float key = (float)ivf_gathered_dot<EL>(rows, a.ld, id, lane, tile, yd);
-            const float wk = __shfl(lk, K - 1);
-            const int wi = __shfl(li, K - 1);
-            unsigned long long m = __ballot(id >= 0 && (cnt < K || ranks_before(key, id, wk, wi)));
-            while (m != 0ull) { // one candidate at a time, the whole wave on it
-                const int c = __ffsll((long long)m) - 1;
-                m &= m - 1ull;
-                const float nk = __shfl(key, c);
-                const int ni = __shfl(id, c);
-                const int at = __popcll(__ballot(lane < cnt && ranks_before(lk, li, nk, ni)));
-                if (at < K) {
-                    const int from = lane > 0 ? lane - 1 : 0;
-                    const float uk = __shfl(lk, from);
-                    const int ui = __shfl(li, from);
-                    if (lane > at) {
-                        lk = uk;
-                        li = ui;
-                    } else if (lane == at) {
-                        lk = nk;
-                        li = ni;
-                    }
-                    cnt = cnt < K ? cnt + 1 : K;
+            if constexpr (FILT) {
+                // admission where the row number is read: bit and label of an in-range row only, then the queue
+                if (id >= 0) {
+                    bool ok = a.sel_bits == nullptr || ivf::bit_is_set(a.sel_bits, a.sel_bit0 + id);
+                    if (ok && a.q_labels != nullptr) ok = ivf::group_admits(a.row_labels[id], qlab, a.grp_mode);
+                    if (!ok) id = -1;
                 }
+                const unsigned long long adm = __ballot(id >= 0);
+                if (id >= 0) queue[ivf::queue_slot(queued, adm, lane)] = id;
+                queued = ivf::queue_after_append(queued, adm);
+                __builtin_amdgcn_wave_barrier(); // (one wave: LDS operations complete in order)
+                if (!ivf::queue_has_pass(queued)) continue; // (uniform over the wave)
+                id = queue[lane];
+                queued = ivf::queue_after_pass(queued);
+                const int next = lane < queued ? queue[ivf::kQueuePass + lane] : -1;
+                __builtin_amdgcn_wave_barrier();
+                if (lane < queued) queue[lane] = next;
+                __builtin_amdgcn_wave_barrier();
             }
+            ivf_score_insert<EL>(rows, a.ld, id, lane, tile, yd, K, lk, li, cnt);
+        }
+        if constexpr (FILT) {
+            if (queued > 0) ivf_score_insert<EL>(rows, a.ld, lane < queued ? queue[lane] : -1, lane, tile, yd, K, lk, li, cnt); // the remainder
         }
     }
     if (lane < cnt) {

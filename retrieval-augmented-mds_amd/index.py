@@ -70,6 +70,12 @@ def route_search(index, q, k: int, **kwargs):
         kwargs = {key: v for key, v in kwargs.items() if key not in ("groups", "group_mode")}
     if "selector" in kwargs and kwargs["selector"] is None:
         kwargs = {key: v for key, v in kwargs.items() if key != "selector"}
+    if hasattr(index, "search_probed"):  # an IvfIndex: the probed lists under the same filters; its nprobe attribute decides
+        if int(k) > _lib.MAX_K:
+            raise NotImplementedError(f"an IVF index serves k <= {_lib.MAX_K} (search_probed); got k = {int(k)}")
+        if kwargs.pop("force_ip", False):
+            raise NotImplementedError("force_ip on an IVF index: the exhaustive cross-check goes to its flat index")
+        return index.search_probed(q, int(k), **kwargs)
     if "selector" in kwargs or "groups" in kwargs:
         return index.search_wide(q, int(k), **kwargs)
     if int(k) > _lib.MAX_K and hasattr(index, "search_wide"):

@@ -218,13 +218,36 @@ class IvfIndex:
         del keep
         return out
 
-    def search_probed(self, x, k: int, nprobe: int | None = None, idx_offset: int = 0):
+    def set_labels(self, labels, row0: int = 0) -> None:
+        """One int32 group label per row (MipsIndex.set_labels on the inner flat index): what groups= of search_probed tests.  The
+        labels follow their rows through remove_ids, save and load; rows added later need theirs before the next grouped search."""
+        self.flat.set_labels(labels, row0)
+
+    def labels(self, row0: int = 0, n: int | None = None) -> np.ndarray:
+        return self.flat.labels(row0, n)
+
+    def labels_of(self, ids, idx_offset: int = 0):
+        return self.flat.labels_of(ids, idx_offset)
+
+    def search_probed(self, x, k: int, nprobe: int | None = None, idx_offset: int = 0, selector=None, groups=None, group_mode: str = "exclude",
+                      sel_bit0: int = 0):
         """(D, I) [nq, k]: for every query the best k of the rows whose list lies in P(q) -- the flat storage's canonical score, ordered
         by (score descending, row ascending), -1 / -inf padding (include/mips_hip_ivf.h).  nprobe defaults to self.nprobe.  NumPy in
-        gives NumPy out; a CUDA tensor in gives CUDA tensors out, stream-ordered (graph-capturable in steady state)."""
+        gives NumPy out; a CUDA tensor in gives CUDA tensors out, stream-ordered (graph-capturable in steady state).
+        selector (a Selector, a list of row ids, a bool mask or a NumPy uint8 bitmap; one for all queries; bit sel_bit0 + i decides row
+        i) and groups (an int array [nq], NumPy -> host, CUDA tensor -> device) with group_mode "exclude" / "only" are those of
+        MipsIndex.search_wide: only admitted rows can be results -- what the search returns on an index from which the others were
+        deleted, row numbers kept.  The rows are refused inside the list scan, so nothing is fetched in excess and dropped."""
         nprobe = int(self.nprobe if nprobe is None else nprobe)
         k = int(k)
         ptr, code, is_dev, nq, keep = self._rows(x, "search_probed")
+        if selector is not None:
+            from .selector import Selector, is_id_list
+
+            if is_id_list(selector):
+                selector = Selector.from_ids(selector, int(sel_bit0) + self.ntotal, device=self.device)
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self.flat._sel_args(selector, sel_bit0, "search_probed")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self.flat._grp_args(groups, group_mode, nq, "search_probed")
         stream = _stream_handle(self.device)
         if is_dev:
             import torch
@@ -238,8 +261,15 @@ class IvfIndex:
             I = np.empty((nq, max(k, 0)), np.int64)
             dp, ip, flags = D.ctypes.data, I.ctypes.data, 0
         with self._mutex:
-            _lib.check(self._lib.mips_ivf_search(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags, stream), "mips_ivf_search")
-        del keep
+            if groups is not None:
+                _lib.check(self._lib.mips_ivf_search_grp(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags | sel_flag | grp_flag,
+                                                         sel_ptr, sel_nbits, int(sel_bit0), grp_ptr, grp_mode, stream), "mips_ivf_search_grp")
+            elif selector is not None:
+                _lib.check(self._lib.mips_ivf_search_sel(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags | sel_flag,
+                                                         sel_ptr, sel_nbits, int(sel_bit0), stream), "mips_ivf_search_sel")
+            else:
+                _lib.check(self._lib.mips_ivf_search(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags, stream), "mips_ivf_search")
+        del keep, sel_keep, grp_keep
         return D, I
 
     # rows by id: the inner flat index's (row ids are the flat ids)

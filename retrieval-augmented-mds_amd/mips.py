@@ -35,6 +35,7 @@ import numpy as np
 
 from . import _lib
 from .index import MipsIndex, l2_normalize_, route_search, rows_max_sumsq, rows_max_sumsq_into
+from .ivf import IvfIndex
 
 METRIC_INNER_PRODUCT = _lib.METRIC_IP
 METRIC_L2 = _lib.METRIC_L2
@@ -68,6 +69,10 @@ class MipsArgs:
     mips_device: int = None
     mips_shard: bool = False  # under an initialised torch.distributed group: row-shard the index over the ranks
     #  instead of replicating it on every rank as lightning_model.py:180 does
+    # > 0: an IVF index of mips_nlist k-means lists over the same storage (IvfIndex; the reference's "IVF256,SQ8" is mips_nlist=256
+    # with mips_string_factory="SQ8"), trained on the first mips_train_size rows, searched over mips_nprobe (default 1) lists per
+    # query.  Approximate by construction -- rows outside the probed lists are not seen -- and exact on the rows it scores.
+    mips_nlist: int = 0
 
 
 @dataclass
@@ -328,6 +333,9 @@ class KnowledgeBase:
         the other rows.  An L2 index takes the stripped (un-augmented) rows, as add_faiss_index stored them.  Indexes that were
         not built by add_faiss_index are joined on their stored rows (rows_raw)."""
         index = self.get_index(index_name).faiss_index
+        if isinstance(index, IvfIndex):
+            raise NotImplementedError("near_duplicates: an IVF index has no range search (the self-join needs every row within the "
+                                      "threshold, not those of the probed lists)")
         column = self._index_columns.get(index_name)
         if column is not None:
             x = np.asarray(self.columns[column], dtype=np.float32)
@@ -362,6 +370,9 @@ class KnowledgeBase:
         renumbered.  Group labels travel with their rows inside the index; the code table of set_groups stays as it is (a value
         whose last row left keeps its code, which no row carries any more).  -> the number of rows dropped."""
         n = len(self)
+        if any(isinstance(h.faiss_index, IvfIndex) for h in self._indexes.values()):
+            raise NotImplementedError("remove_rows: not served on an IVF-backed knowledge base (IvfIndex.remove_ids removes from the "
+                                      "index alone)")
         ids = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
         if ids.size and (ids[0] < 0 or ids[-1] >= n):
             raise ValueError(f"remove_rows: a row lies outside [0, {n})")
@@ -460,6 +471,18 @@ class Mips:
     def _sharded(self) -> bool:
         return bool(self.args.mips_shard) and self._dist()[1] > 1
 
+    def _nlist(self) -> int:
+        """mips_nlist, after refusing what an IVF index does not serve"""
+        nlist = int(getattr(self.args, "mips_nlist", 0) or 0)
+        if nlist <= 0:
+            return 0
+        if self.metric_type != METRIC_INNER_PRODUCT:
+            raise NotImplementedError("mips_nlist with the L2 metric: an IVF index ranks by inner product only (this backend's L2 is the "
+                                      "MIPS->L2 reduction, whose constant is not a property of a list)")
+        if self.args.mips_shard:
+            raise NotImplementedError("mips_nlist with mips_shard: the row-sharded index has no IVF form")
+        return nlist
+
     def init_embeddings_folder(self) -> None:
         """mips.py:246-249 (@rank_zero_only there)."""
         if self._dist()[0] != 0:
@@ -540,6 +563,7 @@ class Mips:
         import torch
 
         dtype = factory_dtype(self.string_factory, self.args.mips_index_dtype)
+        nlist = self._nlist()
         rank, world, up = self._dist()
         if up and rank != 0:
             return
@@ -560,16 +584,22 @@ class Mips:
         if self.normalize and self.metric_type == METRIC_INNER_PRODUCT:
             l2_normalize_(x)
 
-        index = MipsIndex(x.shape[1], metric=self.metric_type, dtype=dtype, device=self.args.mips_device)
-        if dtype == "sq8":   # mips_train_size rows (mips.py:333-340 passes it as train_size), all of them when it is not positive
-            ts = self.train_size if isinstance(self.train_size, int) and self.train_size > 0 else x.shape[0]
+        ts = self.train_size if isinstance(self.train_size, int) and self.train_size > 0 else x.shape[0]
+        if nlist > 0:   # the IVF index by name: k-means (and an SQ8 range) on the first mips_train_size rows, then every row
+            index = IvfIndex(x.shape[1], nlist, dtype=dtype, device=self.args.mips_device)
             index.train(x[:ts])
-        index.reserve(x.shape[0])
-        index.add(x)
-        if self.metric_type == METRIC_L2:
-            self.phi = index.phi()
-        if isinstance(self.args.mips_nprobe, int):
-            index.nprobe = self.args.mips_nprobe
+            index.add(x)
+            index.nprobe = self.args.mips_nprobe or 1
+        else:
+            index = MipsIndex(x.shape[1], metric=self.metric_type, dtype=dtype, device=self.args.mips_device)
+            if dtype == "sq8":   # mips_train_size rows (mips.py:333-340 passes it as train_size), all of them when it is not positive
+                index.train(x[:ts])
+            index.reserve(x.shape[0])
+            index.add(x)
+            if self.metric_type == METRIC_L2:
+                self.phi = index.phi()
+            if isinstance(self.args.mips_nprobe, int):
+                index.nprobe = self.args.mips_nprobe
         cols = dict(self.data) if self.data is not None else (shard_cols or {})
         self.embeddings = KnowledgeBase(cols, index, self.index_name)
 
@@ -577,6 +607,9 @@ class Mips:
     # exchange (mips.py:243-244, 292-295), no second pass: max-norm is a running maximum, the IP normalisation is per
     # row, phi is taken from the finished index -- the result is bit-identical to build_index(all rows at once)
     def begin_index_build(self, d: int) -> None:
+        if self._nlist() > 0:
+            raise NotImplementedError("mips_nlist: the streaming build has no rows to train the lists on before the first add; "
+                                      "build_index() trains and adds")
         if factory_dtype(self.string_factory, self.args.mips_index_dtype) == "sq8":
             raise NotImplementedError("mips_string_factory='SQ8': the streaming build has no rows to train on before the first add; "
                                       "build_index() trains and adds")
@@ -639,6 +672,7 @@ class Mips:
         from .sharded import ShardedMipsIndex
 
         dtype = factory_dtype(self.string_factory, self.args.mips_index_dtype)   # ("SQ8": ShardedMipsIndex refuses it)
+        self._nlist()   # (refuses mips_nlist with mips_shard)
         n = len(embeddings)
         if isinstance(self.args.mips_db_max_size, int):
             n = min(n, self.args.mips_db_max_size)
@@ -750,6 +784,13 @@ class Mips:
             if self.index_name not in self.embeddings._groups:
                 self.embeddings.set_groups(self.index_name, self.index_column)
             groups = self.embeddings.group_codes(self.index_name, ignore_groups, "exclude")
+        if isinstance(index, IvfIndex):   # the probed lists under the group rule, k + 1 and the ignore filter on the device
+            qq = q.detach()
+            qq = l2_normalize_(qq.float().contiguous().clone()) if want_norm else qq.contiguous()
+            kk = k + 1 if ignore_indexes is not None else k
+            kw = {} if groups is None else {"groups": groups, "group_mode": "exclude"}
+            s, i = route_search(index, qq, kk, **kw)
+            return (s, i) if ignore_indexes is None else filter_ignore(s, i, ignore_indexes, k)
         if isinstance(index, MipsIndex):
             # prepare + search + ignore filter in one library call: one kernel launch at the reference's own sizes
             # (B <= 16 queries, ~10^4 documents), the same separate steps otherwise -- identical results
@@ -784,7 +825,7 @@ class Mips:
         import torch
 
         index = self._index()
-        if not isinstance(index, MipsIndex):
+        if not isinstance(index, (MipsIndex, IvfIndex)):
             raise NotImplementedError("retrieved_group_hits reads the labels of an unsharded MipsIndex")
         if self.index_name not in self.embeddings._groups:
             self.embeddings.set_groups(self.index_name, self.index_column)
@@ -801,6 +842,8 @@ class Mips:
         q = np.array(x, dtype=np.float32, copy=True)
         if self.normalize:
             q = self.l2_normalization(q)
+        if isinstance(index, IvfIndex):
+            index = index.flat   # exhaustive: every row, not the probed lists
         return route_search(index, q, k, force_ip=True)  # the reference's cross-check is always an inner product
 
     # ------------------------------------------------------------------ forward (mips.py:402-463)
@@ -875,10 +918,14 @@ class Mips:
         """mips.py:545-549: every rank loads.  The reference loads the WHOLE index on every rank
         (lightning_model.py:180); with mips_shard=True under a process group each rank keeps only its row range
         of the same files (ShardedMipsIndex.load) and searches go through the one all-gather + merge."""
+        nlist = self._nlist()
         if self._sharded():
             from .sharded import ShardedMipsIndex
 
             index = ShardedMipsIndex.load(str(self.index_file), device=self.args.mips_device)
+        elif nlist > 0:
+            index = IvfIndex.load(str(self.index_file), device=self.args.mips_device)
+            index.nprobe = self.args.mips_nprobe or 1
         else:
             index = MipsIndex.load(str(self.index_file), device=self.args.mips_device)
         with open(self.embeddings_folder / "columns.json") as f:
