@@ -44,6 +44,19 @@ __device__ __forceinline__ unsigned lane_id_here() {
     return ln;
 }
 
+// max(a, b, c) of raw MFMA results.  fmaxf() makes the compiler canonicalise every input it cannot prove canonical (one
+// v_max_f32 x, x, x per accumulator); the instruction itself needs none.  An asm statement gets no hazard padding: the caller
+// places it at least 8 wait states after the MFMA that wrote an operand (what hipcc pads a VALU read of this MFMA shape with).
+__device__ __forceinline__ float max3_raw(float a, float b, float c) {
+    float r = a;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+#else
+    (void)b; (void)c;
+#endif
+    return r;
+}
+
 // NT_DOCS: non-temporal document DMA -- for searches of ONE query tile, where every document block has a single reader
 // (the fourth slot held a diagnostic axis, retired; it stays in the parameter list so that the instance names remain the ones
 // profiles/, latest_traffic.json and the tests know)
@@ -125,9 +138,18 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     const __amdgpu_buffer_rsrc_t thr_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(reinterpret_cast<unsigned char*>(p.gthr) + (int64_t)qt * (WAVES * THR_WAVE) - (int64_t)THR_AREA), 0,
         (int)(THR_AREA + WAVES * THR_WAVE), 0x00020000);
+    // ONE_PASS keeps this value in a register (opaque, as lane_off_kept below), so that the bound fetch at the head of a block
+    // costs no vector instruction
+    unsigned thr_addr_kept = 0u;
+    if constexpr (ONE_PASS) {
+        thr_addr_kept = thr_addr_of((unsigned)lane);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(thr_addr_kept));
+#endif
+    }
     auto refresh_thresholds = [&](bool real) { // !real: out-of-range dummy into the dump area (uniform vmcnt count)
         lds_void* dst = (lds_void*)(smem + (real ? THR_AREA + wave * THR_WAVE : DUMP_AREA));
-        const unsigned thr_addr = thr_addr_of(lane_id_here());
+        const unsigned thr_addr = ONE_PASS ? thr_addr_kept : thr_addr_of(lane_id_here());
         __builtin_amdgcn_raw_ptr_buffer_load_lds(thr_rsrc, dst, 16, real ? thr_addr : (thr_addr | 0x40000000u), 0, 0, 16);
     };
 
@@ -169,13 +191,53 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
         const unsigned cc = ln & 15u, gg = ln >> 4;
         return (int)(cc * 128u + ((gg ^ ((cc >> 1) & 7u)) << 4));
     };
+    // ONE_PASS keeps it (opaque); the two read addresses of a block, stage base + rd0 and stage base + (rd0 ^ 64), are made from
+    // it under the last MFMAs of the block before and cross the block boundary in registers
+    unsigned rd0_kept = 0u, rd_even = 0u, rd_odd = 0u;
+    auto set_read_addresses = [&](int stage) {
+        // two instructions, the stage base from an SGPR; as asm, so that the compiler neither keeps rd0 ^ 64 in a register of
+        // its own nor moves the pair to the head of the next block
+        const unsigned base = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)(size_t)(lds_void*)smem + (unsigned)(stage * STAGE_BYTES)));
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("v_add_u32 %0, %3, %2\n\tv_xad_u32 %1, %2, 64, %3" : "=&v"(rd_even), "=v"(rd_odd) : "v"(rd0_kept), "s"(base));
+#else
+        (void)base;
+#endif
+    };
+    if constexpr (ONE_PASS) {
+        rd0_kept = (unsigned)rd0_of((unsigned)lane);
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+v"(rd0_kept));
+#endif
+        set_read_addresses(0);
+    }
 
     // ---- split barrier (see scan_kernel_v3.hpp)
     const unsigned cnt_lds = (unsigned)(size_t)(lds_void*)(smem + DUMP_AREA + 1024);
     unsigned arrivals_needed = 0;
-    constexpr int PER_BLOCK = PPW + 1;
-    auto arrive = [&]() {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 2) * PER_BLOCK) : "memory");
+    // A wave issues PPW document pieces per block, and one bound fetch before them: in every block where DUMMY_FETCH (a fetch of
+    // out-of-range zeros into the dump area stands in on the blocks that refresh nothing), in the refresh blocks alone otherwise.
+    // arrive(fetched) says whether THIS block had the fetch.  The invariant: vmcnt(N) with N = the operations the wave issued in
+    // this block leaves only those outstanding (loads retire in issue order), so everything issued in the block before
+    // -- the pieces of the stage that the next block reads -- has landed when the wave adds itself to the arrival count.
+    // The prologue (one bound fetch + PPW pieces per ring stage) and the idle waves' loop count the same way.
+    static_assert(STAGES == 3, "arrive() lets the operations of one block stay in flight");
+    constexpr bool DUMMY_FETCH = !ONE_PASS;
+    auto arrive = [&](int fetched) { // 0 or 1, uniform
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (ONE_PASS) {
+            // one straight statement: lane 0 alone adds (every lane of the wave is active here), without the compiler's branch
+            // around a masked-off region.  The wait of a block that fetched nothing is skipped by a branch that only the refresh
+            // blocks take; vmcnt(PPW + 1) after vmcnt(PPW) waits for nothing.
+            uint64_t exec_kept;
+            asm volatile("s_cmp_lg_u32 %3, 0\n\ts_cbranch_scc1 1f\n\ts_waitcnt vmcnt(%4)\n1:\n\ts_waitcnt vmcnt(%5)\n\t"
+                         "s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_add_u32 %1, %2\n\ts_mov_b64 exec, %0"
+                         : "=&s"(exec_kept) : "v"(cnt_lds), "v"(1u), "s"(fetched), "n"(PPW), "n"(PPW + 1) : "memory", "scc");
+            return;
+        }
+#endif
+        if (fetched) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW + 1) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
 #if defined(__HIP_DEVICE_COMPILE__)
         if (lane == 0) asm volatile("ds_add_u32 %0, %1" ::"v"(cnt_lds), "v"(1u) : "memory");
 #endif
@@ -193,6 +255,28 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
                 break;
             }
             __builtin_amdgcn_s_sleep(1);
+        }
+    };
+    // ONE_PASS: the same polls in the same order, laid out so that "count reached" at the first poll falls through into the
+    // block; the sleeping polls and the spin-limit error path stand aside
+    auto reached = [&]() {
+        unsigned v = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(v) : "v"(cnt_lds) : "memory");
+#endif
+        return __builtin_amdgcn_readfirstlane(v) >= arrivals_needed;
+    };
+    auto wait_all_straight = [&]() {
+        arrivals_needed += WAVES;
+        if (__builtin_expect(!reached(), 0)) {
+            for (int spin = 0;; ++spin) {
+                if (spin > p.spin_limit) {
+                    if (lane == 0) *p.err = 1u;
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(1);
+                if (reached()) break;
+            }
         }
     };
 
@@ -226,14 +310,11 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     };
 
     // ONE_PASS: epilogue of the whole 32-document block.  acc[half][n] = documents 16 half + 4 g .. + 3 against query 16 n + c.
-    // The fast path (8 max, 2 compares, one branch) falls through; the insert path is one loop per query that visits only the
+    // mx0, mx1 = the largest of the lane's eight accumulators for query c and for query 16 + c (block(): half_max, block_max).
+    // The fast path (2 compares, one branch) falls through; the insert path is one loop per query that visits only the
     // accumulators above the bound, lowest document first (the order the strict-'>' tie rule needs), through ONE copy of
     // list_insert -- a select chain picks the score, so the path stays a few hundred bytes instead of sixteen inlined inserts.
-    auto epilogue_block = [&](f32x4 (&acc)[2][2], int blk) {
-        const float mx0 = fmaxf(fmaxf(fmaxf(acc[0][0][0], acc[0][0][1]), fmaxf(acc[0][0][2], acc[0][0][3])),
-                                fmaxf(fmaxf(acc[1][0][0], acc[1][0][1]), fmaxf(acc[1][0][2], acc[1][0][3])));
-        const float mx1 = fmaxf(fmaxf(fmaxf(acc[0][1][0], acc[0][1][1]), fmaxf(acc[0][1][2], acc[0][1][3])),
-                                fmaxf(fmaxf(acc[1][1][0], acc[1][1][1]), fmaxf(acc[1][1][2], acc[1][1][3])));
+    auto epilogue_block = [&](f32x4 (&acc)[2][2], int blk, float mx0, float mx1) {
         if (__builtin_expect(__ballot((int)(mx0 > thr[0]) | (int)(mx1 > thr[1])) != 0ull, 0)) { // '|': no lane-level short circuit
             const unsigned thr_addr = thr_addr_of(lane_id_here());
             const int base = blk * V3_DB + (int)((thr_addr >> 6) & 12u); // + 4 g, from the lane bits
@@ -262,27 +343,42 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
         }
     };
 
-    auto block = [&](bool refresh, int blk, int stage, const unsigned char* pbase, int pstage) {
-        if (idle_wave) { // all of this wave's queries are padding (scan_kernel_v3.hpp): bring the documents, skip the arithmetic
-            refresh_thresholds(false);
-            issue(pbase, pstage);
-            arrive();
-            return;
+    // first block of the index that holds rows past its end: (blk + 1) * 32 > ntotal <=> blk >= ntotal / 32 (uniform, scalar)
+    const int first_ragged = (int)(p.ntotal / V3_DB < 0x7fffffff ? p.ntotal / V3_DB : 0x7fffffff);
+    auto block = [&](int refresh_word, int blk, int stage, const unsigned char* pbase, int pstage) { // refresh_word: 0 or 1
+        const bool refresh = refresh_word != 0;
+        if constexpr (!ONE_PASS) {
+            if (idle_wave) { // all of this wave's queries are padding (scan_kernel_v3.hpp): bring the documents, skip the arithmetic
+                refresh_thresholds(false);
+                issue(pbase, pstage);
+                arrive(1);
+                return;
+            }
         }
         const unsigned char* sa = smem + stage * STAGE_BYTES;
-        const int rd0 = rd0_of(lane_id_here());
+        const int rd0 = ONE_PASS ? 0 : rd0_of(lane_id_here());
         // flattened step t = half * KS32 + s
         auto lds_frag = [&](int t) {
             const int half = t / KS32, s = t % KS32;
+            if constexpr (ONE_PASS) { // the kept addresses are LDS byte addresses, stage base included: the rest is the immediate
+                typedef const __attribute__((address_space(3))) bf16x8 lds_frag_t;
+                return *(lds_frag_t*)(size_t)(((s & 1) ? rd_odd : rd_even) + (unsigned)(half * 2048 + (s >> 1) * 4096));
+            }
             const int off = half * 2048 + (s >> 1) * 4096 + ((s & 1) ? (rd0 ^ 64) : rd0);
             return *reinterpret_cast<const bf16x8*>(sa + off);
         };
+        // ONE_PASS: the head of a block is its first two fragment reads, from addresses that are already in registers; no
+        // vector instruction stands between the poll and them, and the MFMA chain starts as soon as they land
         bf16x8 ar[AD];
 #pragma unroll
         for (int t = 0; t < AD; ++t) ar[t] = lds_frag(t);
-        refresh_thresholds(refresh); // first VMEM op of the block
+        if constexpr (DUMMY_FETCH) {
+            refresh_thresholds(refresh); // first VMEM op of the block
+        } else {
+            if (__builtin_expect(refresh, 0)) refresh_thresholds(true); // first VMEM op of a refresh block; the others fetch nothing
+        }
         __builtin_amdgcn_sched_barrier(0);
-        const bool ragged = (int64_t)(blk + 1) * V3_DB > p.ntotal; // uniform
+        const bool ragged = ONE_PASS ? blk >= first_ragged : (int64_t)(blk + 1) * V3_DB > p.ntotal; // uniform
         auto mask_ragged = [&](f32x4 (&a)[2], int half) { // last block of the index only: rows past the end score -inf
             const int base = blk * V3_DB + 16 * half + 4 * (int)(lane_id_here() >> 4);
 #pragma unroll
@@ -293,6 +389,11 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
                 }
         };
         f32x4 accs[2][2]; // [half][n]; without ONE_PASS a half's accumulators die in its own epilogue
+        // ONE_PASS pre-test: the largest of a lane's 8 accumulators per query, 4 v_max3_f32 each.  The two that reduce half 0
+        // run under the MFMAs of half 1 (5 and 7 steps after the last MFMA of half 0: its results have long landed)
+        float mh[2] = {0.f, 0.f};
+        auto half_max = [&](const f32x4& a) { return max3_raw(max3_raw(a[0], a[1], a[2]), a[3], a[3]); };
+        auto block_max = [&](float m, const f32x4& a) { return max3_raw(max3_raw(m, a[0], a[1]), a[2], a[3]); };
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             f32x4(&acc)[2] = accs[half];
@@ -307,13 +408,23 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
                 acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ar[t % AD], bq[1][s], acc[1], 0, 0, 0);
                 if (t + AD < STEPS) ar[t % AD] = lds_frag(t + AD);
                 if ((t % (STEPS / PPW)) == (STEPS / PPW) / 2) issue_piece(pbase, pstage, t / (STEPS / PPW));
+                if constexpr (ONE_PASS) {
+                    if (t == KS32 + 5) mh[0] = half_max(accs[0][0]);
+                    if (t == KS32 + 7) mh[1] = half_max(accs[0][1]);
+                    // the last fragment read of this block is issued: the next block's read addresses take the registers over
+                    if (t == STEPS - AD) set_read_addresses(stage == STAGES - 1 ? 0 : stage + 1);
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (half == 1) arrive(); // all LDS reads of this block are done; the epilogue runs un-synchronised
-            if (half == 1 && refresh) {
+            // all LDS reads of this block are done: arrive; the epilogue runs un-synchronised
+            if (half == 1) arrive(DUMMY_FETCH ? 1 : refresh_word);
+            if (half == 1 && (ONE_PASS ? __builtin_expect(refresh, 0) : refresh)) {
                 // minimum of the 8 class words of queries c and 16 + c (what an earlier block's DMA brought, or 0);
                 // inline asm, one query at a time: see scan_kernel_v3.hpp
-                const unsigned thr_addr = thr_addr_of(lane_id_here());
+                unsigned thr_addr = ONE_PASS ? thr_addr_kept : thr_addr_of(lane_id_here());
+#if defined(__HIP_DEVICE_COMPILE__)
+                if constexpr (ONE_PASS) asm volatile("" : "+v"(thr_addr)); // (derive a0 here, not in a register kept for it)
+#endif
                 const unsigned a0 = (unsigned)(size_t)(lds_void*)smem + (thr_addr & ~0x3FFu) + ((thr_addr & 0xF0u) << 1);
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {
@@ -336,11 +447,21 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
             }
         }
         if constexpr (ONE_PASS) { // after arrive() and the bound refresh: one top-k pass over both halves
-            if (ragged) {
+            if (__builtin_expect(ragged, 0)) {
                 mask_ragged(accs[0], 0);
                 mask_ragged(accs[1], 1);
+                mh[0] = half_max(accs[0][0]); // of the masked values
+                mh[1] = half_max(accs[0][1]);
             }
-            epilogue_block(accs, blk);
+            // The last two MFMAs wrote accs[1][0] and accs[1][1].  An asm statement gets no hazard padding, and the compiler pads
+            // a VALU read of this MFMA shape with 8 wait states: arrive() stands in between (volatile asm keeps its order; its
+            // statement is 7 instructions on its shortest path), the s_nop adds 4, query 16 + c waits 2 more.
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("s_nop 3" ::: "memory");
+#endif
+            const float mx0 = block_max(mh[0], accs[1][0]);
+            const float mx1 = block_max(mh[1], accs[1][1]);
+            epilogue_block(accs, blk, mx0, mx1);
         }
     };
 
@@ -350,7 +471,7 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     constexpr int AHEAD = STAGES - 1;
     if (nb > 0) {
 #pragma unroll
-        for (int a = 0; a < AHEAD; ++a) { // same operation sequence as steady-state blocks (vmcnt arithmetic)
+        for (int a = 0; a < AHEAD; ++a) { // same operation sequence as a refresh block (vmcnt arithmetic)
             refresh_thresholds(true);
             issue(a < nb ? first + a * blk_bytes : last, a);
         }
@@ -359,13 +480,41 @@ __global__ __launch_bounds__(512, 2) void scan_kernel_v4(ScanArgs p) {
     int stage = 0, pstage = AHEAD;
     if (tid == 0) *reinterpret_cast<unsigned*>(smem + DUMP_AREA + 1024) = 0u;
     __syncthreads();
-    if (nb > 0) arrive();
-    for (int i = 0; i < nb; ++i) {
-        wait_all();
-        block(i < 8 || (i & 7) == 0, b0 + i, stage, pbase, pstage); // refresh schedule: scan_kernel_v3.hpp
+    if (nb > 0) arrive(1);
+    auto advance = [&](int i) {
         if (i + AHEAD + 1 < nb) pbase += blk_bytes;
         stage = stage == STAGES - 1 ? 0 : stage + 1;
         pstage = pstage == STAGES - 1 ? 0 : pstage + 1;
+    };
+    if constexpr (ONE_PASS) {
+        // idle_wave is constant per wave: decided once, outside the block loop.  An idle wave (all of its queries are padding,
+        // scan_kernel_v3.hpp) brings its share of the documents and takes part in the block barrier, nothing else
+        if (idle_wave) {
+            for (int i = 0; i < nb; ++i) {
+                wait_all_straight();
+                issue(pbase, pstage);
+                arrive(0);
+                advance(i);
+            }
+        } else {
+            for (int i = 0; i < nb; ++i) {
+                wait_all_straight();
+                // refresh schedule (scan_kernel_v3.hpp): i < 8 || (i & 7) == 0, as a word made by scalar arithmetic and kept in
+                // an SGPR, so that arrive() reads it there and no lane mask of it is turned into a word after the chain
+                int refresh_word = (int)(((unsigned)(i - 8) >> 31) | ((unsigned)((i & 7) - 1) >> 31));
+#if defined(__HIP_DEVICE_COMPILE__)
+                asm volatile("" : "+s"(refresh_word));
+#endif
+                block(refresh_word, b0 + i, stage, pbase, pstage);
+                advance(i);
+            }
+        }
+    } else {
+        for (int i = 0; i < nb; ++i) {
+            wait_all();
+            block(i < 8 || (i & 7) == 0 ? 1 : 0, b0 + i, stage, pbase, pstage); // refresh schedule: scan_kernel_v3.hpp
+            advance(i);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
