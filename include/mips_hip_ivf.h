@@ -119,6 +119,34 @@ int mips_ivf_search_grp(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq,
                         int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels,
                         int grp_mode, void* hip_stream);
 
+/* The WIDE search over the probed lists: mips_ivf_search / _sel / _grp with 1 <= k <= MIPS_MAX_K_WIDE -- for measuring recall@100
+ * against the flat index when choosing nprobe, for retrieve-then-rerank, and for mining hard negatives ("the best 64 rows that are
+ * not of my article": q_labels with MIPS_GRP_EXCLUDE) at IVF cost.  The definition is the one above, word for word: P(q_j), A_j,
+ * admitted_j, the best k of A_j n admitted_j by the storage's canonical score (SQ8 ranked and merged on S, turned into D once the
+ * order is fixed), order (score descending, row ascending), -1 / -inf padding, idx_offset added.  Nothing is approximated and
+ * nothing is certified: every probed row is scored exactly, so unlike mips_search_wide on a flat index the call needs no
+ * approximate pass, no candidate pool and no certificate -- only a wider exact selection inside the list scan.  Hence:
+ *   - prefix: for k' <= k the first k' columns equal the call with k', bit for bit; for k' <= MIPS_MAX_K they equal
+ *     mips_ivf_search / _sel / _grp with k' (for k <= MIPS_MAX_K the call issues exactly their launches);
+ *   - every list probed: on a BF16 or F32 index with nprobe >= nlist the result is mips_search_wide / _sel / _grp on mips_ivf_flat
+ *     under the same filter, bit for bit;
+ *   - scores by id: mips_score_subset on mips_ivf_flat reproduces the scores;
+ *   - no filter: with sel_bits == NULL and q_labels == NULL, mips_ivf_search_wide_grp IS mips_ivf_search_wide (same launches, same
+ *     bits).  A bitmap alone is q_labels == NULL: there is no third entry point.
+ * Arguments, flags, host / device forms and synchronisation are those of mips_ivf_search / mips_ivf_search_grp.
+ * MIPS_E_INVALID: what mips_ivf_search_grp refuses, k < 1, MIPS_OUT_PACKED (it would serve a sharded IVF index, which does not
+ * exist).  MIPS_E_UNSUPPORTED: k > MIPS_MAX_K_WIDE, min(nprobe, nlist) > 1024, and min(nprobe, nlist) * k > 65536 -- the entries
+ * per query mips_merge_topk_sorted_packed takes.  nq == 0: MIPS_OK.  An empty index: padding.
+ * The launch sequence is that of mips_ivf_search -- probe, staging, ONE list-scan launch of nq * p * S workgroups, the merge of the
+ * p * S sorted partial lists of k entries, the finishing pass -- with, for k > MIPS_MAX_K, the wide list scan as its third launch:
+ * every wave keeps its best k in a pool in LDS (64, 256 or 1024 slots, the smallest that holds k) instead of in registers.  The
+ * capture contract of mips_ivf_search / _grp holds unchanged. */
+int mips_ivf_search_wide(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                         int64_t idx_offset, int flags, void* hip_stream);
+int mips_ivf_search_wide_grp(mips_ivf_t* ivf, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                             int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels,
+                             int grp_mode, void* hip_stream);
+
 /* mips_index_remove on the inner index, the same order-preserving compaction of the assignments, the list table rebuilt.
  * Arguments as mips_index_remove (include/mips_hip_update.h); out_counts[0] = rows removed. */
 int mips_ivf_remove(mips_ivf_t* ivf, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, int flags, int64_t out_counts[2],

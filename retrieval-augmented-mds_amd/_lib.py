@@ -181,6 +181,8 @@ def _bind(lib):
         "mips_ivf_search": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp]),
         "mips_ivf_search_sel": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp, i64, i64, vp]),
         "mips_ivf_search_grp": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp, i64, i64, vp, i32, vp]),
+        "mips_ivf_search_wide": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp]),
+        "mips_ivf_search_wide_grp": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp, i64, i64, vp, i32, vp]),
     }
     for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
@@ -209,7 +211,7 @@ EXPORTS_SQ8 = ("mips_index_sq8_train", "mips_index_sq8_set_params", "mips_index_
 EXPORTS_IVF = ("mips_ivf_create", "mips_ivf_destroy", "mips_ivf_flat", "mips_ivf_train", "mips_ivf_is_trained", "mips_ivf_set_centroids",
                "mips_ivf_get_centroids", "mips_ivf_add", "mips_ivf_probe", "mips_ivf_remove", "mips_ivf_reset",
                "mips_ivf_list_sizes", "mips_ivf_read_assign", "mips_ivf_set_assign", "mips_ivf_set_param", "mips_ivf_nlist",
-               "mips_ivf_search", "mips_ivf_search_sel", "mips_ivf_search_grp")  # mips_hip_ivf.h
+               "mips_ivf_search", "mips_ivf_search_sel", "mips_ivf_search_grp", "mips_ivf_search_wide", "mips_ivf_search_wide_grp")  # mips_hip_ivf.h
 
 
 def range_record_words(nq: int, stride: int) -> int:

@@ -152,9 +152,23 @@ int ivf_query_args(const char* who, const mips_ivf* v, const void* q, int q_dtyp
     return MIPS_OK;
 }
 
+// launch 3 of a wide search (MIPS_MAX_K < k <= MIPS_MAX_K_WIDE): the instance whose pools hold KP >= k entries
+template <int KP>
+void ivf_launch_wide_scan(bool filtered, bool f32x, bool sq8, unsigned grid, hipStream_t st, const mips::IvfScanArgs& a) {
+    constexpr int threads = 64 * mips::IVF_SCAN_WAVES;
+    if (filtered) {
+        if (f32x) mips::ivf_list_scan_wide_kernel<mips::ElemF32, mips::ElemF32, true, KP><<<grid, threads, 0, st>>>(a);
+        else if (sq8) mips::ivf_list_scan_wide_kernel<mips::ElemU8, mips::ElemBF16, true, KP><<<grid, threads, 0, st>>>(a);
+        else mips::ivf_list_scan_wide_kernel<mips::ElemBF16, mips::ElemBF16, true, KP><<<grid, threads, 0, st>>>(a);
+    } else if (f32x) mips::ivf_list_scan_wide_kernel<mips::ElemF32, mips::ElemF32, false, KP><<<grid, threads, 0, st>>>(a);
+    else if (sq8) mips::ivf_list_scan_wide_kernel<mips::ElemU8, mips::ElemBF16, false, KP><<<grid, threads, 0, st>>>(a);
+    else mips::ivf_list_scan_wide_kernel<mips::ElemBF16, mips::ElemBF16, false, KP><<<grid, threads, 0, st>>>(a);
+}
+
 // mips_ivf_search (sel_bits == nullptr and q_labels == nullptr: the unfiltered launch sequence, nothing else is touched) and
-// mips_ivf_search_sel / _grp: the same sequence with the filtered instance of the list scan
-int ivf_search_impl(const char* who, mips_ivf* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+// mips_ivf_search_sel / _grp: the same sequence with the filtered instance of the list scan.  wide (mips_ivf_search_wide / _grp):
+// k up to MIPS_MAX_K_WIDE; the same sequence again, with the wide list scan as launch 3 when k > MIPS_MAX_K
+int ivf_search_impl(const char* who, bool wide, mips_ivf* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
                     int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels, int grp_mode,
                     void* hip_stream) {
     int rc = ivf_check(who, v);
@@ -162,7 +176,14 @@ int ivf_search_impl(const char* who, mips_ivf* v, const void* q, int q_dtype, in
     if (mips_ivf_is_trained(v) != 1) return fail(MIPS_E_INVALID, "%s: the IVF index is not trained (mips_ivf_train / mips_ivf_set_centroids)", who);
     int p = 0;
     if ((rc = ivf_query_args(who, v, q, q_dtype, nq, nprobe, &p))) return rc;
-    if (k < 1 || k > MIPS_MAX_K) return fail(MIPS_E_INVALID, "%s: k must be 1 .. %d, got %d", who, MIPS_MAX_K, k);
+    if (wide) {
+        if (k < 1) return fail(MIPS_E_INVALID, "%s: k must be 1 .. %d, got %d", who, MIPS_MAX_K_WIDE, k);
+        if (flags & MIPS_OUT_PACKED) return fail(MIPS_E_INVALID, "%s: MIPS_OUT_PACKED is not served on an IVF index", who);
+        if (k > MIPS_MAX_K_WIDE) return fail(MIPS_E_UNSUPPORTED, "%s: k = %d exceeds MIPS_MAX_K_WIDE = %d", who, k, MIPS_MAX_K_WIDE);
+        if ((int64_t)p * k > ivf::kMergeLimit)
+            return fail(MIPS_E_UNSUPPORTED, "%s: min(nprobe, nlist) * k = %d * %d exceeds %lld, the entries per query the merge of the partial lists takes", who,
+                        p, k, (long long)ivf::kMergeLimit);
+    } else if (k < 1 || k > MIPS_MAX_K) return fail(MIPS_E_INVALID, "%s: k must be 1 .. %d, got %d", who, MIPS_MAX_K, k);
     mips_index* ix = v->flat;
     const bool filtered = sel_bits != nullptr || q_labels != nullptr;
     Selector sel;
@@ -246,7 +267,12 @@ int ivf_search_impl(const char* who, mips_ivf* v, const void* q, int q_dtype, in
         a.grp_mode = sel.grp_only ? MIPS_GRP_ONLY : MIPS_GRP_EXCLUDE;
         const unsigned grid = (unsigned)(ns * parts); // <= 4096 * 1024, or < 2 * cus * 32
         constexpr int threads = 64 * mips::IVF_SCAN_WAVES;
-        if (filtered) {
+        if (k > MIPS_MAX_K) { // (wide only) the pool class of k: ivf::pool_class
+            const int kp = ivf::pool_class(k);
+            if (kp == 64) ivf_launch_wide_scan<64>(filtered, f32x, ix->sq8, grid, st, a);
+            else if (kp == 256) ivf_launch_wide_scan<256>(filtered, f32x, ix->sq8, grid, st, a);
+            else ivf_launch_wide_scan<1024>(filtered, f32x, ix->sq8, grid, st, a);
+        } else if (filtered) {
             if (f32x) mips::ivf_list_scan_kernel<mips::ElemF32, mips::ElemF32, true><<<grid, threads, 0, st>>>(a);
             else if (ix->sq8) mips::ivf_list_scan_kernel<mips::ElemU8, mips::ElemBF16, true><<<grid, threads, 0, st>>>(a);
             else mips::ivf_list_scan_kernel<mips::ElemBF16, mips::ElemBF16, true><<<grid, threads, 0, st>>>(a);
@@ -563,20 +589,33 @@ int mips_ivf_probe(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int64_
 
 int mips_ivf_search(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx, int64_t idx_offset,
                     int flags, void* hip_stream) {
-    return ivf_search_impl("mips_ivf_search", v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, nullptr, 0, 0, nullptr, 0, hip_stream);
+    return ivf_search_impl("mips_ivf_search", false, v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, nullptr, 0, 0, nullptr, 0, hip_stream);
 }
 
 int mips_ivf_search_sel(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
                         int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, void* hip_stream) {
-    return ivf_search_impl("mips_ivf_search_sel", v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, sel_bits, sel_nbits, sel_bit0, nullptr,
+    return ivf_search_impl("mips_ivf_search_sel", false, v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, sel_bits, sel_nbits, sel_bit0, nullptr,
                            0, hip_stream);
 }
 
 int mips_ivf_search_grp(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
                         int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels, int grp_mode,
                         void* hip_stream) {
-    return ivf_search_impl(q_labels ? "mips_ivf_search_grp" : "mips_ivf_search_sel", v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags,
+    return ivf_search_impl(q_labels ? "mips_ivf_search_grp" : "mips_ivf_search_sel", false, v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags,
                            sel_bits, sel_nbits, sel_bit0, q_labels, grp_mode, hip_stream);
+}
+
+int mips_ivf_search_wide(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                         int64_t idx_offset, int flags, void* hip_stream) {
+    return ivf_search_impl("mips_ivf_search_wide", true, v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, nullptr, 0, 0, nullptr, 0,
+                           hip_stream);
+}
+
+int mips_ivf_search_wide_grp(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
+                             int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels,
+                             int grp_mode, void* hip_stream) {
+    return ivf_search_impl("mips_ivf_search_wide_grp", true, v, q, q_dtype, nq, k, nprobe, out_scores, out_idx, idx_offset, flags, sel_bits, sel_nbits, sel_bit0,
+                           q_labels, grp_mode, hip_stream);
 }
 
 } // extern "C"

@@ -43,6 +43,7 @@
 #include "sq8_scan_kernel.hpp"
 #include "ivf_kernels.hpp"
 #include "ivf_search_kernels.hpp"
+#include "ivf_wide_kernels.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"

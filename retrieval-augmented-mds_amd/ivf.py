@@ -272,6 +272,47 @@ class IvfIndex:
         del keep, sel_keep, grp_keep
         return D, I
 
+    def search_probed_wide(self, x, k: int, nprobe: int | None = None, idx_offset: int = 0, selector=None, groups=None, group_mode: str = "exclude",
+                           sel_bit0: int = 0):
+        """search_probed for 1 <= k <= MAX_K_WIDE (include/mips_hip_ivf.h: mips_ivf_search_wide / _grp): the same definition, the same
+        arguments, the same contract -- NumPy in gives NumPy out; a CUDA tensor in gives CUDA tensors out, stream-ordered
+        (graph-capturable in steady state).  Every probed row is scored exactly, so nothing is approximated or certified; for k' <= k
+        the first k' columns are the result for k', and for k' <= MAX_K those of search_probed.  Raises NotImplementedError for
+        k > MAX_K_WIDE (as MipsIndex.search_wide does) and RuntimeError for what the library refuses, min(nprobe, nlist) * k > 65536
+        among it."""
+        nprobe = int(self.nprobe if nprobe is None else nprobe)
+        k = int(k)
+        if k > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"search_probed_wide: k = {k} exceeds MAX_K_WIDE = {_lib.MAX_K_WIDE}")
+        ptr, code, is_dev, nq, keep = self._rows(x, "search_probed_wide")
+        if selector is not None:
+            from .selector import Selector, is_id_list
+
+            if is_id_list(selector):
+                selector = Selector.from_ids(selector, int(sel_bit0) + self.ntotal, device=self.device)
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self.flat._sel_args(selector, sel_bit0, "search_probed_wide")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self.flat._grp_args(groups, group_mode, nq, "search_probed_wide")
+        stream = _stream_handle(self.device)
+        if is_dev:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            D = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+            I = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+            dp, ip, flags = D.data_ptr(), I.data_ptr(), _lib.Q_DEVICE | _lib.OUT_DEVICE
+        else:
+            D = np.empty((nq, max(k, 0)), np.float32)
+            I = np.empty((nq, max(k, 0)), np.int64)
+            dp, ip, flags = D.ctypes.data, I.ctypes.data, 0
+        with self._mutex:
+            if selector is not None or groups is not None:  # a bitmap alone is q_labels == NULL
+                _lib.check(self._lib.mips_ivf_search_wide_grp(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags | sel_flag | grp_flag,
+                                                              sel_ptr, sel_nbits, int(sel_bit0), grp_ptr, grp_mode, stream), "mips_ivf_search_wide_grp")
+            else:
+                _lib.check(self._lib.mips_ivf_search_wide(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags, stream), "mips_ivf_search_wide")
+        del keep, sel_keep, grp_keep
+        return D, I
+
     # rows by id: the inner flat index's (row ids are the flat ids)
     def reconstruct(self, key: int):
         return self.flat.reconstruct(key)
