@@ -33,6 +33,7 @@
  *                    nprobe >= nlist gives mips_search's result on mips_ivf_flat bit for bit.  Every row of the probed lists is
  *                    scored exactly (the sequential fp64 sum); nothing is approximated and nothing needs a certificate.
  * Refused: MIPS_METRIC_L2 (the index ranks by inner product), d > 1024, the e4m3 storages, nlist outside 1 .. 65536, p > 1024.
+ * The range form -- every probed, admitted row above a per-query radius, in CSR form -- is declared in mips_hip_ivf_range.h.
  */
 #ifndef MIPS_HIP_IVF_H
 #define MIPS_HIP_IVF_H

@@ -24,6 +24,7 @@ HEADER_ROWS = os.path.join(_ROOT, "include", "mips_hip_rows.h")  # stored rows, 
 HEADER_HOOK = os.path.join(_ROOT, "include", "mips_hip_hook.h")  # the one-launch hook search under a group filter
 HEADER_SQ8 = os.path.join(_ROOT, "include", "mips_hip_sq8.h")  # the trained 8-bit scalar quantiser of an SQ8 index
 HEADER_IVF = os.path.join(_ROOT, "include", "mips_hip_ivf.h")  # the IVF index: k-means lists over a flat index, nprobe
+HEADER_IVF_RANGE = os.path.join(_ROOT, "include", "mips_hip_ivf_range.h")  # range search over the probed lists of an IVF index
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -31,6 +32,7 @@ DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3, DTYPE_FP8_E4M3_DOCS, DTYPE_SQ8 = 0, 1, 2,
 METRIC_IP, METRIC_L2 = 0, 1
 Q_DEVICE, OUT_DEVICE, OUT_PACKED, FORCE_IP, SEL_DEVICE, GRP_DEVICE = 1, 2, 4, 8, 16, 32
 IDS_DEVICE, ROWS_ZERO_MISSING = 64, 128  # include/mips_hip_rows.h
+RADII_DEVICE = 256  # include/mips_hip_ivf_range.h
 GRP_EXCLUDE, GRP_ONLY = 0, 1  # MIPS_GRP_*: the mode of a grouped search
 LABEL_NONE = -(1 << 31)  # MIPS_LABEL_NONE = INT32_MIN: a query that is not group-filtered
 SYNTH_LATTICE, SYNTH_GAUSS, SYNTH_LATTICE_FP8 = 0, 1, 2
@@ -44,7 +46,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -184,7 +186,11 @@ def _bind(lib):
         "mips_ivf_search_wide": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp]),
         "mips_ivf_search_wide_grp": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp, i64, i64, vp, i32, vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf}.items():
+    sig_ivf_range = {  # include/mips_hip_ivf_range.h
+        "mips_ivf_range_search": (i32, [vp, vp, i32, i64, vp, i64, vp, vp, vp, i64, i64, i32, vp]),
+        "mips_ivf_range_search_grp": (i32, [vp, vp, i32, i64, vp, i64, vp, vp, vp, i64, i64, i32, vp, i64, i64, vp, i32, vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -212,6 +218,7 @@ EXPORTS_IVF = ("mips_ivf_create", "mips_ivf_destroy", "mips_ivf_flat", "mips_ivf
                "mips_ivf_get_centroids", "mips_ivf_add", "mips_ivf_probe", "mips_ivf_remove", "mips_ivf_reset",
                "mips_ivf_list_sizes", "mips_ivf_read_assign", "mips_ivf_set_assign", "mips_ivf_set_param", "mips_ivf_nlist",
                "mips_ivf_search", "mips_ivf_search_sel", "mips_ivf_search_grp", "mips_ivf_search_wide", "mips_ivf_search_wide_grp")  # mips_hip_ivf.h
+EXPORTS_IVF_RANGE = ("mips_ivf_range_search", "mips_ivf_range_search_grp")  # include/mips_hip_ivf_range.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:

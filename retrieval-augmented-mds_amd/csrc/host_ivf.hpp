@@ -17,6 +17,16 @@ struct IvfSearchScratch {
     Buffer sel, qlab;         // a host bitmap and host query labels of a filtered call (mips_ivf_search_sel / _grp)
 };
 
+// What a range search over the probed lists (host_ivf_range.hpp) writes between its launches, beside the probe and the staged
+// queries above.  It grows only when a call asks for a larger (nq, cap).
+struct IvfRangeScratch {
+    Buffer words;             // [0] staging cursor of the slice, [1] hits of the slices before it
+    Buffer counts;            // [2][ns] hits and placed records of every query of the slice
+    Buffer radii;             // [nq] host radii
+    Buffer stage;             // [cap] records: query, row, score
+    Buffer lims, out_s, out_i; // [nq + 1], [cap], [cap] of a host-output call
+};
+
 struct mips_ivf {
     int device = 0;
     int64_t d = 0;
@@ -35,6 +45,7 @@ struct mips_ivf {
     Buffer cs, ci;              // coarse results [nq][p]
     Buffer train_rows, train_assign, train_off, train_list, flag;
     IvfSearchScratch ss;        // mips_ivf_search, and the device-output form of mips_ivf_probe
+    IvfRangeScratch rs;         // mips_ivf_range_search
     int cus = 1;                // compute units of the device (sizes the list scan)
     ~mips_ivf() {
         if (flat) (void)mips_index_destroy(flat);

@@ -23,6 +23,7 @@
 #include "../../include/mips_hip_hook.h"
 #include "../../include/mips_hip_sq8.h"
 #include "../../include/mips_hip_ivf.h"
+#include "../../include/mips_hip_ivf_range.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -44,6 +45,7 @@
 #include "ivf_kernels.hpp"
 #include "ivf_search_kernels.hpp"
 #include "ivf_wide_kernels.hpp"
+#include "ivf_range_kernels.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"
@@ -1092,3 +1094,4 @@ int mips_scan_timing(mips_index_t* ix, float* out_sum_ms, int* out_count, int re
 } // extern "C"
 
 #include "host_ivf.hpp" // the IVF index (include/mips_hip_ivf.h): its own entry points, behind everything they call
+#include "host_ivf_range.hpp" // its range search (include/mips_hip_ivf_range.h)

@@ -2,8 +2,9 @@
 
 Building and maintaining the file: deterministic k-means training, the list of every added row, the list table, the probed lists
 P(q) of a query, removal, reset, save / load.  Searching it: `search_probed` scores every row of the probed lists exactly and
-returns what `flat.search` would return if the other rows were deleted; `flat` is the inner MipsIndex over the same rows and
-searches all of them.
+returns what `flat.search` would return if the other rows were deleted; `range_search_probed` returns every probed row above a
+per-query radius in CSR form (include/mips_hip_ivf_range.h); `flat` is the inner MipsIndex over the same rows and searches all of
+them.
 
 All arithmetic happens in libmips_hip.so; this file moves pointers.  No CPU fallback.
 """
@@ -312,6 +313,97 @@ class IvfIndex:
                 _lib.check(self._lib.mips_ivf_search_wide(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags, stream), "mips_ivf_search_wide")
         del keep, sel_keep, grp_keep
         return D, I
+
+    # ------------------------------------------------------------------ range search over the probed lists
+    def _range_radii(self, radius, nq: int):
+        """-> (pointer, flag, keepalive): a CUDA float32 tensor [nq] is read where it is (MIPS_RADII_DEVICE); anything else becomes
+        host float32 [nq], a NaN refused"""
+        import torch
+
+        if isinstance(radius, torch.Tensor) and radius.is_cuda:
+            if radius.dtype != torch.float32 or radius.dim() != 1 or radius.shape[0] != nq or not radius.is_contiguous() or radius.device.index != self.device:
+                raise ValueError(f"range_search_probed: device radii must be a contiguous CUDA float32 tensor [{nq}] on cuda:{self.device}")
+            return radius.data_ptr(), _lib.RADII_DEVICE, radius
+        r = MipsIndex._radii(radius, nq)
+        return r.ctypes.data, 0, r
+
+    def range_search_probed_into(self, x, radius, lims, D, I, nprobe: int | None = None, idx_offset: int = 0, selector=None, groups=None,
+                                 group_mode: str = "exclude", sel_bit0: int = 0) -> None:
+        """The non-synchronising form of range_search_probed (include/mips_hip_ivf_range.h): the caller allocates the CUDA tensors lims
+        (int64 [nq + 1]), D (float32 [cap]) and I (int64 [cap]); everything is enqueued on the current stream, so with CUDA queries
+        (and CUDA radii, groups and a device selector) the call may be captured into a graph.  lims always receives the true counts;
+        when lims[-1] > cap the contents of D and I are unspecified and the call is to be repeated with larger tensors.  cap = 0
+        (empty D and I) is a counting call.  `radius`: a scalar, nq host values, or a CUDA float32 tensor [nq] that is read on the
+        device (a NaN there makes its query hit nothing; a host NaN raises)."""
+        import torch
+
+        nprobe = int(self.nprobe if nprobe is None else nprobe)
+        ptr, code, is_dev, nq, keep = self._rows(x, "range_search_probed")
+        if selector is not None:
+            from .selector import Selector, is_id_list
+
+            if is_id_list(selector):
+                selector = Selector.from_ids(selector, int(sel_bit0) + self.ntotal, device=self.device)
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self.flat._sel_args(selector, sel_bit0, "range_search_probed")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self.flat._grp_args(groups, group_mode, nq, "range_search_probed")
+        rad_ptr, rad_flag, rad_keep = self._range_radii(radius, nq)
+        dev = torch.device("cuda", self.device)
+        for t, dt, what in ((lims, torch.int64, "lims"), (D, torch.float32, "D"), (I, torch.int64, "I")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dt and t.dim() == 1 and t.is_contiguous()):
+                raise ValueError(f"range_search_probed_into: {what} must be a contiguous 1-d CUDA {dt} tensor on cuda:{self.device}")
+        if lims.shape[0] != nq + 1 or D.shape[0] != I.shape[0]:
+            raise ValueError(f"range_search_probed_into: lims must have {nq + 1} entries and D, I one length")
+        cap = int(D.shape[0])
+        flags = _lib.OUT_DEVICE | (_lib.Q_DEVICE if is_dev else 0) | rad_flag
+        dp, ip = (D.data_ptr(), I.data_ptr()) if cap else (None, None)
+        stream = _stream_handle(self.device)
+        with self._mutex:
+            if selector is not None or groups is not None:  # a bitmap alone is q_labels == NULL
+                _lib.check(self._lib.mips_ivf_range_search_grp(self._h, ptr, code, nq, rad_ptr, nprobe, lims.data_ptr(), dp, ip, cap, int(idx_offset),
+                                                               flags | sel_flag | grp_flag, sel_ptr, sel_nbits, int(sel_bit0), grp_ptr, grp_mode, stream),
+                           "mips_ivf_range_search_grp")
+            else:
+                _lib.check(self._lib.mips_ivf_range_search(self._h, ptr, code, nq, rad_ptr, nprobe, lims.data_ptr(), dp, ip, cap, int(idx_offset), flags,
+                                                           stream), "mips_ivf_range_search")
+        del keep, sel_keep, grp_keep, rad_keep
+
+    def range_search_probed(self, x, radius, nprobe: int | None = None, idx_offset: int = 0, selector=None, groups=None, group_mode: str = "exclude",
+                            sel_bit0: int = 0):
+        """(lims, D, I): for every query the rows of the probed lists that the filter admits and whose reported score is strictly above
+        the radius (include/mips_hip_ivf_range.h) -- the flat storage's canonical score, an 'sq8' index's D -- in CSR form as
+        MipsIndex.range_search returns it: the hits of query j are D / I [lims[j] : lims[j + 1]], in ascending row order.  `radius` is
+        a scalar, nq values, or a CUDA float32 tensor [nq].  NumPy in gives NumPy out; a CUDA tensor in gives CUDA tensors out.  The
+        result's size is not known beforehand: a first call runs with a guessed capacity, lims[-1] is READ ON THE HOST -- THIS
+        SYNCHRONISES the stream -- and one repeat with the exact size follows if the guess was too small
+        (range_search_probed_into is the form that never synchronises).  selector, groups, group_mode, sel_bit0: as search_probed."""
+        import torch
+
+        from .selector import Selector, is_id_list
+
+        if selector is not None and not isinstance(selector, (Selector, np.ndarray)):   # packed once for the repeat call
+            selector = Selector.from_ids(selector, int(sel_bit0) + self.ntotal, device=self.device) if is_id_list(selector) else \
+                Selector.from_mask(selector, device=self.device)
+        if isinstance(selector, np.ndarray) and selector.dtype != np.uint8:
+            selector = Selector.from_mask(selector, device=self.device)
+        ptr, code, is_dev, nq, keep = self._rows(x, "range_search_probed")
+        if not (isinstance(radius, torch.Tensor) and radius.is_cuda):
+            radius = MipsIndex._radii(radius, nq)
+        dev = f"cuda:{self.device}"
+        lims = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        cap = max(1 << 16, 256 * nq)
+        while True:
+            D = torch.empty(cap, dtype=torch.float32, device=dev)
+            I = torch.empty(cap, dtype=torch.int64, device=dev)
+            self.range_search_probed_into(keep, radius, lims, D, I, nprobe=nprobe, idx_offset=idx_offset, selector=selector, groups=groups,
+                                          group_mode=group_mode, sel_bit0=sel_bit0)
+            total = int(lims[-1].item())   # the synchronisation
+            if total <= cap:
+                break
+            cap = total
+        D, I = D[:total], I[:total]
+        if is_dev:
+            return lims, D.clone() if total < cap else D, I.clone() if total < cap else I
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
 
     # rows by id: the inner flat index's (row ids are the flat ids)
     def reconstruct(self, key: int):
