@@ -34,6 +34,8 @@
  *                    scored exactly (the sequential fp64 sum); nothing is approximated and nothing needs a certificate.
  * Refused: MIPS_METRIC_L2 (the index ranks by inner product), d > 1024, the e4m3 storages, nlist outside 1 .. 65536, p > 1024.
  * The range form -- every probed, admitted row above a per-query radius, in CSR form -- is declared in mips_hip_ivf_range.h.
+ * Overwriting stored rows by id, with their assignments following (faiss IndexIVF::update_vectors), is mips_ivf_update in
+ * mips_hip_write.h; like mips_ivf_add it ends the validity of a captured search.
  */
 #ifndef MIPS_HIP_IVF_H
 #define MIPS_HIP_IVF_H

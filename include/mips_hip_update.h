@@ -1,6 +1,7 @@
 /* mips_hip_update.h -- entry points that change the rows an index already holds.
  *
- * mips_hip.h appends (mips_index_add*) and forgets everything (mips_index_reset); this header takes single rows out.
+ * mips_hip.h appends (mips_index_add*) and forgets everything (mips_index_reset); this header takes single rows out, and
+ * mips_hip_write.h gives stored rows a new value in place (mips_index_update, mips_ivf_update: row numbers and labels stay).
  * Conventions, error codes and mips_last_error() are those of mips_hip.h; the same libmips_hip.so exports everything and
  * there is one ABI version, defined there.
  */

@@ -25,6 +25,7 @@ HEADER_HOOK = os.path.join(_ROOT, "include", "mips_hip_hook.h")  # the one-launc
 HEADER_SQ8 = os.path.join(_ROOT, "include", "mips_hip_sq8.h")  # the trained 8-bit scalar quantiser of an SQ8 index
 HEADER_IVF = os.path.join(_ROOT, "include", "mips_hip_ivf.h")  # the IVF index: k-means lists over a flat index, nprobe
 HEADER_IVF_RANGE = os.path.join(_ROOT, "include", "mips_hip_ivf_range.h")  # range search over the probed lists of an IVF index
+HEADER_WRITE = os.path.join(_ROOT, "include", "mips_hip_write.h")  # stored rows overwritten in place by id (flat and IVF index)
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -46,7 +47,7 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE, HEADER_WRITE]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -190,7 +191,11 @@ def _bind(lib):
         "mips_ivf_range_search": (i32, [vp, vp, i32, i64, vp, i64, vp, vp, vp, i64, i64, i32, vp]),
         "mips_ivf_range_search_grp": (i32, [vp, vp, i32, i64, vp, i64, vp, vp, vp, i64, i64, i32, vp, i64, i64, vp, i32, vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range}.items():
+    sig_write = {  # include/mips_hip_write.h
+        "mips_index_update": (i32, [vp, vp, i64, i64, vp, i32, i32, vp, vp]),
+        "mips_ivf_update": (i32, [vp, vp, i64, i64, vp, i32, i32, vp, vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range, **sig_write}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -219,6 +224,7 @@ EXPORTS_IVF = ("mips_ivf_create", "mips_ivf_destroy", "mips_ivf_flat", "mips_ivf
                "mips_ivf_list_sizes", "mips_ivf_read_assign", "mips_ivf_set_assign", "mips_ivf_set_param", "mips_ivf_nlist",
                "mips_ivf_search", "mips_ivf_search_sel", "mips_ivf_search_grp", "mips_ivf_search_wide", "mips_ivf_search_wide_grp")  # mips_hip_ivf.h
 EXPORTS_IVF_RANGE = ("mips_ivf_range_search", "mips_ivf_range_search_grp")  # include/mips_hip_ivf_range.h, likewise
+EXPORTS_WRITE = ("mips_index_update", "mips_ivf_update")  # include/mips_hip_write.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:

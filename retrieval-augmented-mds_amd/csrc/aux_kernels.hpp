@@ -179,6 +179,13 @@ __global__ void convert_rows_f8_kernel(const SRC* __restrict__ src, int64_t n, i
 // fp32-exact mode: split fp32 (or bf16) rows [n][d] (pitch src_ld) into bf16 planes dst [n][2 * plane] =
 // [hi | lo], hi = bf16(x), lo = bf16(x - hi) (x - hi is exact in fp32), columns >= d zero; optionally keep
 // the fp32 originals in keep [n][plane] for the exact re-score.
+// one element of the split (split_rows_kernel, and update_scatter_kernel on a row written in place)
+__device__ __forceinline__ void split_hi_lo(float x, uint16_t& hi, uint16_t& lo) {
+    hi = f32_to_bf16_rne(x);
+    const float r = x - bf16_bits_to_f32(hi);
+    lo = (x == x && fabsf(x) != INFINITY) ? f32_to_bf16_rne(r) : (uint16_t)0; // inf - inf / NaN: keep lo = 0
+}
+
 template <typename SRC>
 __global__ void split_rows_kernel(const SRC* __restrict__ src, int64_t n, int d, int src_ld, uint16_t* dst, int plane,
                                   float* keep) {
@@ -197,9 +204,7 @@ __global__ void split_rows_kernel(const SRC* __restrict__ src, int64_t n, int d,
                 if constexpr (sizeof(SRC) == 4) x = ((const float*)src)[row * src_ld + c];
                 else x = bf16_bits_to_f32(((const uint16_t*)src)[row * src_ld + c]);
             }
-            hi[e] = f32_to_bf16_rne(x);
-            const float r = x - bf16_bits_to_f32(hi[e]);
-            lo[e] = (x == x && fabsf(x) != INFINITY) ? f32_to_bf16_rne(r) : (uint16_t)0; // inf - inf / NaN: keep lo = 0
+            split_hi_lo(x, hi[e], lo[e]);
             if (keep) keep[row * plane + c] = x;
         }
         u32x4 oh, ol;
@@ -286,21 +291,26 @@ __global__ void synth_fill_kernel(void* out, int64_t n, int d, int ld, int64_t r
 }
 
 // ------------------------------------------------------------------ phi = max row |x|^2 (fp64, sequential)
+// |x|^2 of one stored row (row_sumsq_max_kernel, and update_finish_kernel on a row written in place)
+template <typename EL>
+__device__ __forceinline__ double row_sumsq(const typename EL::type* x, int ld) {
+    double acc = 0.0;
+    for (int c = 0; c < ld; c += EL::PER16) { // sequential in the column index: the oracle's order
+        const u32x4 v = *reinterpret_cast<const u32x4*>(x + c);
+#pragma unroll
+        for (int e = 0; e < EL::PER16; ++e) {
+            const double a = (double)EL::get(v, e);
+            acc += a * a;
+        }
+    }
+    return acc;
+}
+
 template <typename EL>
 __global__ void row_sumsq_max_kernel(const typename EL::type* rows, int64_t n, int ld, unsigned long long* out_bits) {
     const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     double acc = 0.0; // rows past the end contribute 0 (the maximum of non-negative values is unaffected)
-    if (r < n) {
-        const typename EL::type* x = rows + r * ld;
-        for (int c = 0; c < ld; c += EL::PER16) { // sequential in the column index: the oracle's order
-            const u32x4 v = *reinterpret_cast<const u32x4*>(x + c);
-#pragma unroll
-            for (int e = 0; e < EL::PER16; ++e) {
-                const double a = (double)EL::get(v, e);
-                acc += a * a;
-            }
-        }
-    }
+    if (r < n) acc = row_sumsq<EL>(rows + r * ld, ld);
     // one atomic per wave, not per row (a million atomics on one word take ~12 ms): the maximum is exact in any
     // order; non-negative doubles order like their bit patterns
 #pragma unroll
@@ -309,21 +319,24 @@ __global__ void row_sumsq_max_kernel(const typename EL::type* rows, int64_t n, i
 }
 
 // max_i |x_i - bf16(x_i)|^2 over fp32 rows (two-stage fp32-exact search: how far the bf16 scan's operand is from the row)
+__device__ __forceinline__ double row_resid_sumsq(const float* x, int ld) {
+    double acc = 0.0;
+    for (int c = 0; c < ld; c += 4) {
+        const u32x4 v = *reinterpret_cast<const u32x4*>(x + c);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xe = __uint_as_float(v[e]);
+            const double a = (double)xe - (double)bf16_bits_to_f32(f32_to_bf16_rne(xe));
+            acc += a * a;
+        }
+    }
+    return acc;
+}
+
 __global__ void row_resid_sumsq_max_kernel(const float* rows, int64_t n, int ld, unsigned long long* out_bits) {
     const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     double acc = 0.0;
-    if (r < n) {
-        const float* x = rows + r * ld;
-        for (int c = 0; c < ld; c += 4) {
-            const u32x4 v = *reinterpret_cast<const u32x4*>(x + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float xe = __uint_as_float(v[e]);
-                const double a = (double)xe - (double)bf16_bits_to_f32(f32_to_bf16_rne(xe));
-                acc += a * a;
-            }
-        }
-    }
+    if (r < n) acc = row_resid_sumsq(rows + r * ld, ld);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) acc = fmax(acc, __shfl_xor(acc, off));
     if ((threadIdx.x & 63) == 0) atomicMax(out_bits, (unsigned long long)__double_as_longlong(acc));

@@ -44,6 +44,7 @@ struct mips_ivf {
     Buffer count;               // [nlist] histogram of a table build
     Buffer cs, ci;              // coarse results [nq][p]
     Buffer train_rows, train_assign, train_off, train_list, flag;
+    Buffer upd_assign;          // mips_ivf_update: the list of every position's row [n]
     IvfSearchScratch ss;        // mips_ivf_search, and the device-output form of mips_ivf_probe
     IvfRangeScratch rs;         // mips_ivf_range_search
     int cus = 1;                // compute units of the device (sizes the list scan)
@@ -564,6 +565,30 @@ int mips_ivf_remove(mips_ivf_t* v, const uint8_t* sel_bits, int64_t sel_nbits, i
     if ((rc = ivf_rebuild(v, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return MIPS_OK;
+}
+
+// include/mips_hip_write.h: the rows by id through the flat index, the list of every written row with them, the table again
+int mips_ivf_update(mips_ivf_t* v, const int64_t* ids, int64_t n, int64_t idx_offset, const void* rows, int src_dtype, int flags, int64_t* out_updated,
+                    void* hip_stream) {
+    int rc = ivf_check("mips_ivf_update", v);
+    if (rc) return rc;
+    if (src_dtype == MIPS_DTYPE_SQ8 || src_dtype == MIPS_DTYPE_FP8_E4M3)
+        return fail(MIPS_E_UNSUPPORTED, "mips_ivf_update: raw codes cannot be assigned to a list (float32 or bf16 rows)");
+    if (src_dtype != MIPS_DTYPE_F32 && src_dtype != MIPS_DTYPE_BF16) return fail(MIPS_E_INVALID, "mips_ivf_update: src_dtype must be F32 or BF16");
+    if (n < 0 || (n > 0 && (!ids || !rows))) return fail(MIPS_E_INVALID, "mips_ivf_update: bad ids / rows / n");
+    if (mips_ivf_is_trained(v) != 1) return fail(MIPS_E_INVALID, "mips_ivf_update: the IVF index is not trained (mips_ivf_train)");
+    if (!upd::count_ok(n)) return fail(MIPS_E_UNSUPPORTED, "mips_ivf_update: more than 2^31 - 1 positions in one call");
+    DeviceGuard g(v->device);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    mips_index* ix = v->flat;
+    if (n == 0 || ix->ntotal == 0) return mips_index_update(ix, ids, n, idx_offset, rows, src_dtype, flags, out_updated, st);
+    if ((rc = v->upd_assign.ensure((size_t)n * sizeof(int)))) return rc;
+    if ((rc = ivf_assign_rows(v, rows, n, src_dtype, (flags & MIPS_Q_DEVICE) != 0, (int*)v->upd_assign.p, st))) return rc;
+    {
+        ORDER_ON(ix, st);
+        if ((rc = index_update(ix, ids, n, idx_offset, rows, src_dtype, flags, out_updated, st, (const int*)v->upd_assign.p, v->assign))) return rc;
+    }
+    return ivf_rebuild(v, st);
 }
 
 int mips_ivf_probe(mips_ivf_t* v, const void* q, int q_dtype, int64_t nq, int64_t nprobe, int32_t* out_lists, int flags, void* hip_stream) {

@@ -187,6 +187,11 @@ struct mips_index {
     int64_t opt_remove_window = 0;
     // rows by id (include/mips_hip_rows.h, host_rows.hpp): the device copy of host ids, and the device result of a host-output call
     Buffer row_ids, row_out;
+    // rows overwritten by id (include/mips_hip_write.h, host_update.hpp; host ids stage into row_ids, host rows into stage): one
+    // int32 per row of `capacity`, -1 between calls (the position that writes the row while a call runs), and the call's count
+    DeviceArray<int> upd_owner;
+    int64_t upd_owner_cap = 0;
+    Buffer upd_count;
     // grouped searches (mips_search_wide_grp / mips_range_search_grp): one int32 label per row in storage of its own, allocated in
     // whole 128-row tiles for at least `capacity` rows (mips_index_set_labels grows it and keeps what it held, so it survives the
     // growth of the rows); rows [0, nlabelled) carry a label.  grp_q: the staged per-query labels of the call in flight.

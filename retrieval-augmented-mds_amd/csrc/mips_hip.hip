@@ -24,6 +24,7 @@
 #include "../../include/mips_hip_sq8.h"
 #include "../../include/mips_hip_ivf.h"
 #include "../../include/mips_hip_ivf_range.h"
+#include "../../include/mips_hip_write.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -46,6 +47,7 @@
 #include "ivf_search_kernels.hpp"
 #include "ivf_wide_kernels.hpp"
 #include "ivf_range_kernels.hpp"
+#include "update_kernels.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"
@@ -58,6 +60,7 @@
 #include "remove_plan.hpp"
 #include "host_remove.hpp"
 #include "host_rows.hpp"
+#include "host_update.hpp"
 
 extern "C" {
 
@@ -839,6 +842,21 @@ int mips_index_remove(mips_index_t* ix, const uint8_t* sel_bits, int64_t sel_nbi
     const hipStream_t st = (hipStream_t)hip_stream;
     ORDER_ON(ix, st);
     return index_remove(ix, sel_bits, sel_nbits, sel_bit0, (flags & MIPS_SEL_DEVICE) != 0, out_counts, st);
+}
+
+// ---- include/mips_hip_write.h
+int mips_index_update(mips_index_t* ix, const int64_t* ids, int64_t n, int64_t idx_offset, const void* rows, int src_dtype, int flags,
+                      int64_t* out_updated, void* hip_stream) {
+    if (!ix) return fail(MIPS_E_INVALID, "mips_index_update: index is NULL");
+    if (n < 0 || (n > 0 && (!ids || !rows))) return fail(MIPS_E_INVALID, "mips_index_update: bad ids / rows / n");
+    if (!src_dtype_ok(ix, src_dtype))
+        return fail(MIPS_E_INVALID, "mips_index_update: src_dtype must be F32 or BF16 (or FP8_E4M3 bytes for an fp8 index, SQ8 codes for an SQ8 index)");
+    if (ix->sq8 && !ix->sq8_trained) return fail(MIPS_E_INVALID, "mips_index_update: the SQ8 index is not trained (mips_index_sq8_train)");
+    if (!upd::count_ok(n)) return fail(MIPS_E_UNSUPPORTED, "mips_index_update: more than 2^31 - 1 positions in one call");
+    DeviceGuard g(ix->device);
+    const hipStream_t st = (hipStream_t)hip_stream;
+    ORDER_ON(ix, st);
+    return index_update(ix, ids, n, idx_offset, rows, src_dtype, flags, out_updated, st);
 }
 
 // ---- include/mips_hip_rows.h

@@ -202,21 +202,38 @@ class IndexFlat:
             return 0
         return self._inner.remove_ids(np.packbits(removal_mask(sel, self._inner.ntotal), bitorder="little"))
 
-    def add(self, x) -> None:
+    def _stored_form(self, x, what: str):
+        """float32 rows [n, d] as the backend stores them: L2 rows are checked to be phi-augmented and lose that column."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"add: expected [n, {self.d}], got {x.shape}")
+            raise ValueError(f"{what}: expected [n, {self.d}], got {x.shape}")
         if self.metric_type == METRIC_L2:
             sq = np.square(x.astype(np.float64)).sum(axis=1)
             phi = getattr(self, "_phi_seen", None)
             ref = float(sq.max()) if phi is None else phi
             if not (len(sq) > 0 and np.all(np.abs(sq - ref) <= 1e-4 * max(ref, 1e-30)) and (x[:, -1] >= 0).all()):
                 raise NotImplementedError(
-                    "IndexFlat(METRIC_L2).add: the rows are not phi-augmented (constant norm, last column sqrt(phi - |x|^2) as "
+                    f"IndexFlat(METRIC_L2).{what}: the rows are not phi-augmented (constant norm, last column sqrt(phi - |x|^2) as "
                     "augment_xb produces, sotasum/mips.py:59-65); this backend's L2 is that MIPS->L2 reduction")
             self._phi_seen = ref
             x = np.ascontiguousarray(x[:, :-1])
+        return x
+
+    def add(self, x) -> None:
+        x = self._stored_form(x, "add")   # (checked before the backend is touched)
         self._index().add(x)
+
+    def update_vectors(self, ids, x) -> int:
+        """faiss IndexIVF.update_vectors(ids, x), served on every index class: row ids[p] takes the value x[p] in place (a
+        repeated id: its last occurrence); row numbers and ntotal stay.  Unlike faiss, an id outside [0, ntotal) raises
+        nothing and writes nothing.  L2: the rows are phi-augmented as for add(), and phi follows the stored rows, so the
+        index equals one built from the final rows.  -> the number of distinct rows written."""
+        ids = np.asarray(ids)
+        if ids.ndim != 1:
+            raise ValueError(f"update_vectors: expected ids [n], got {ids.shape}")
+        if len(ids) == 0 or self._inner is None:
+            return 0
+        return self._inner.update_rows(ids, self._stored_form(x, "update_vectors"), return_count=True)
 
     def search(self, x, k: int, params=None, **kwargs):
         """(D float32 [nq, k], I int64 [nq, k]); NumPy in, NumPy out -- the call of mips.py:383-386 and of HF's search_batch.

@@ -264,6 +264,34 @@ class MipsIndex:
         del keep
         return int(counts[0])
 
+    def _update_args(self, ids, x, what: str):
+        """(ids pointer, rows pointer, n, dtype code, flags, keepalives) of mips_index_update / mips_ivf_update."""
+        iptr, shape, ids_dev, keep_ids = self._ids_arg(ids, what)
+        if len(shape) != 1:
+            raise ValueError(f"{what}: expected ids [n], got {shape}")
+        xptr, code, x_dev, n, keep_x = self._as_buffer(x, "add")   # (rows are taken as add() takes them, raw codes included)
+        if n != shape[0]:
+            raise ValueError(f"{what}: {shape[0]} ids for {n} rows")
+        flags = (_lib.IDS_DEVICE if ids_dev else 0) | (_lib.Q_DEVICE if x_dev else 0)
+        return iptr, xptr, n, code, flags, (keep_ids, keep_x)
+
+    def update_rows(self, ids, x, idx_offset: int = 0, return_count: bool = False):
+        """Overwrite stored rows in place (mips_index_update): for p = 0 .. n - 1, row ids[p] - idx_offset becomes x[p], converted
+        as add() converts it.  An id that names no local row (negative, below idx_offset, past the index) is skipped; of several
+        positions that name one row the last wins.  Row numbers, labels and ntotal stay; afterwards the index equals a fresh one
+        that was given the final rows -- stored bytes and every search, bit for bit.  ids: an integer array [n] (NumPy ->
+        host, CUDA tensor -> device); x [n, d] as add() takes it, host or device.  With CUDA ids and rows and return_count=False
+        nothing synchronises (an L2 index recomputes phi in its next search).  return_count=True -> the number of distinct rows
+        written (synchronises)."""
+        iptr, xptr, n, code, flags, keep = self._update_args(ids, x, "update_rows")
+        count = ctypes.c_int64(0)
+        with self._mutex:
+            _lib.check(self._lib.mips_index_update(self._h, iptr, n, int(idx_offset), xptr, code, flags,
+                                                   ctypes.byref(count) if return_count else None, _stream_handle(self.device)),
+                       "mips_index_update")
+        del keep
+        return int(count.value) if return_count else None
+
     def set_labels(self, labels, row0: int = 0) -> None:
         """One int32 group label per row for rows [row0, row0 + len(labels)) (NumPy or torch int array, host or CUDA): what
         groups= of search_wide / range_search tests.  The labelled rows are a prefix of the index -- row0 may not lie behind

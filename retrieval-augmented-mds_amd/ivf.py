@@ -180,6 +180,25 @@ class IvfIndex:
         del keep
         return int(counts[0])
 
+    def update_rows(self, ids, x, idx_offset: int = 0, return_count: bool = False):
+        """faiss IndexIVF.update_vectors: MipsIndex.update_rows on the stored rows, and every written row moves to the list add()
+        would give its new value (mips_ivf_update); the list table is rebuilt.  float32 / bfloat16 values only, as add().
+        Afterwards the index equals a fresh IvfIndex with the same centroids that was given the final rows.  flat.update_rows
+        alone changes the row and leaves it in its old list."""
+        if not self.is_trained:
+            raise RuntimeError("update_rows: the IvfIndex is not trained (train(x) first, as faiss requires)")
+        xptr, code, x_dev, n, keep = self._rows(x, "update_rows")  # (refuses raw codes)
+        iptr, shape, ids_dev, keep_ids = self.flat._ids_arg(ids, "update_rows")
+        if shape != (n,):
+            raise ValueError(f"update_rows: ids {shape} for {n} rows")
+        flags = (_lib.IDS_DEVICE if ids_dev else 0) | (_lib.Q_DEVICE if x_dev else 0)
+        count = ctypes.c_int64(0)
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_update(self._h, iptr, n, int(idx_offset), xptr, code, flags,
+                                                 ctypes.byref(count) if return_count else None, _stream_handle(self.device)), "mips_ivf_update")
+        del keep, keep_ids
+        return int(count.value) if return_count else None
+
     def list_sizes(self) -> np.ndarray:
         out = np.empty(self._nlist, np.int64)
         with self._mutex:

@@ -364,6 +364,49 @@ class KnowledgeBase:
         order = np.lexsort((j, i))
         return i[order], j[order], s[order]
 
+    def update_rows(self, index_name: str, rows, embeddings) -> None:
+        """Gives the listed rows new embeddings in place, in the index and -- if the base holds the column the index was built
+        from (add_faiss_index) -- in that column: row rows[p] takes embeddings[p]; of a repeated row the last occurrence stays.
+        Row numbers, the other columns and the group labels do not change.  The index is updated by its own method:
+        update_rows_global on a row-sharded index (every rank makes the call with the same arguments), IvfIndex.update_rows
+        (the rows move to the lists of their new values), MipsIndex.update_rows otherwise.  embeddings [n, d'] have the form of
+        the indexed column: an L2 index takes phi-augmented rows and stores them without their last column, as
+        add_faiss_index does (a matrix of the index's own width is taken as already stripped).  Host rows are checked against
+        [0, N); CUDA ids go to the index as they are (an id that names no row is skipped) and nothing synchronises."""
+        import torch
+
+        index = self.get_index(index_name).faiss_index
+        dev_ids = isinstance(rows, torch.Tensor) and rows.is_cuda
+        ids = rows if dev_ids else np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int64).reshape(-1)
+        if not dev_ids and ids.size and (ids.min() < 0 or ids.max() >= index.ntotal):
+            raise ValueError(f"update_rows: a row lies outside [0, {index.ntotal})")
+        x = embeddings if isinstance(embeddings, torch.Tensor) else np.asarray(embeddings, dtype=np.float32)
+        if x.ndim != 2 or x.shape[0] != (ids.numel() if dev_ids else ids.size):
+            raise ValueError(f"update_rows: embeddings {tuple(x.shape)} for {ids.numel() if dev_ids else ids.size} rows")
+        full = x
+        if index.metric_type == METRIC_L2 and x.shape[1] == index.d + 1:
+            if bool((x[:, -1] < 0).any()):
+                raise NotImplementedError("update_rows(L2 index): the rows are not phi-augmented (last column sqrt(phi - |x|^2) >= 0)")
+            x = x[:, :-1]
+        column = self._index_columns.get(index_name)
+        col = self.columns.get(column) if column is not None else None
+        if isinstance(col, np.ndarray) and (col.ndim != 2 or col.shape[1] != full.shape[1]):
+            raise ValueError(f"update_rows: column {column!r} has shape {col.shape}, the embeddings {full.shape[1]} columns")
+        if hasattr(index, "update_rows_global"):
+            index.update_rows_global(ids, x)
+        elif hasattr(index, "update_rows"):
+            index.update_rows(ids, x)
+        elif hasattr(index, "update_vectors"):
+            index.update_vectors(ids, full.detach().cpu().numpy() if isinstance(full, torch.Tensor) else full)
+        else:
+            raise ValueError(f"update_rows: index {index_name!r} cannot overwrite rows")
+        if col is not None:
+            host_ids = ids.cpu().numpy().reshape(-1) if dev_ids else ids
+            vals = full.detach().float().cpu().numpy() if isinstance(full, torch.Tensor) else full
+            for p, r in enumerate(host_ids):   # the sequential loop: a repeated row keeps its last value
+                if 0 <= r < len(col):
+                    col[int(r)] = vals[p]
+
     def remove_rows(self, rows) -> int:
         """Drops the listed rows (int ids, duplicates allowed) from every column and from every attached index
         (remove_ids_global on a row-sharded index, remove_ids otherwise): the surviving rows keep their order and are
@@ -602,6 +645,35 @@ class Mips:
                 index.nprobe = self.args.mips_nprobe
         cols = dict(self.data) if self.data is not None else (shard_cols or {})
         self.embeddings = KnowledgeBase(cols, index, self.index_name)
+
+    def refresh_embeddings(self, rows, embeddings) -> None:
+        """Rolling refresh of a trained retrieval encoder: the knowledge-base rows `rows` (int ids [n]) were re-encoded to
+        `embeddings` [n, d] and are written back in place -- instead of the reference's mips_rebuild_every, which re-encodes and
+        re-adds everything.  The rows are prepared as build_index prepares them (float32 on the device, normalised for a
+        normalised inner-product index; the caller's tensor is not touched) and go through KnowledgeBase.update_rows, so the
+        flat, the IVF and the row-sharded index are all served (sharded: every rank makes the call with the same arguments).
+        Searches afterwards equal those of an index rebuilt from the refreshed matrix; an IVF index keeps its trained lists
+        (and an SQ8 storage its trained range).  max_norm grows if a refreshed row exceeds it and never shrinks; phi (L2) is
+        read again from the index."""
+        import torch
+
+        if self.embeddings is None:
+            raise RuntimeError("Mips: no index (call build_index() or load() first)")
+        dev = f"cuda:{_lib.require_gpu(self.args.mips_device)}"
+        x = torch.as_tensor(embeddings)
+        if x.dim() != 2:
+            raise ValueError(f"refresh_embeddings: expected embeddings [n, d], got {tuple(x.shape)}")
+        y = x.to(dev, dtype=torch.float32).contiguous()
+        if isinstance(embeddings, torch.Tensor) and y.data_ptr() == embeddings.data_ptr():
+            y = y.clone()  # the normalisation below is in place; never touch the caller's tensor
+        if y.shape[0] > 0:
+            new_max = float(np.sqrt(rows_max_sumsq(y)))
+            self.max_norm = new_max if self.max_norm is None else max(self.max_norm, new_max)
+            if self.normalize and self.metric_type == METRIC_INNER_PRODUCT:
+                l2_normalize_(y)
+        self.embeddings.update_rows(self.index_name, rows, y)
+        if self.metric_type == METRIC_L2 and self._index().ntotal > 0:
+            self.phi = self._index().phi()
 
     # ---- streaming form (SURVEY.md 8 f2): CLS vectors go into the index AS THE ENCODER PRODUCES THEM, no Arrow-on-disk
     # exchange (mips.py:243-244, 292-295), no second pass: max-norm is a running maximum, the IP normalisation is per

@@ -182,6 +182,16 @@ class ShardedMipsIndex:
         self._sync_phi()
         return before - self.ntotal_global
 
+    def update_rows_global(self, ids, x) -> None:
+        """COLLECTIVE MipsIndex.update_rows: every rank passes the same GLOBAL row ids [n] and the same rows x [n, d]; each
+        shard writes the rows it holds (ids outside [lo, hi) name no local row and are skipped; lo follows remove_ids_global,
+        as in reconstruct_batch).  Row numbers, labels and the shard sizes stay.  An inner-product index needs no communication
+        and, with CUDA ids and rows, nothing synchronises; an L2 index agrees on the new phi (one scalar all-reduce)."""
+        if self.local is None:
+            raise ValueError("update_rows_global needs the library's own local index (injected steps hold no rows)")
+        self.local.update_rows(ids, x, idx_offset=self.lo)
+        self._sync_phi()
+
     def set_labels_global(self, labels) -> None:
         """Every rank sees the full [N] int array of row labels (MipsIndex.set_labels) and keeps those of its own rows."""
         if len(labels) != self.ntotal_global:
