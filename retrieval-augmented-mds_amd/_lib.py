@@ -26,6 +26,7 @@ HEADER_SQ8 = os.path.join(_ROOT, "include", "mips_hip_sq8.h")  # the trained 8-b
 HEADER_IVF = os.path.join(_ROOT, "include", "mips_hip_ivf.h")  # the IVF index: k-means lists over a flat index, nprobe
 HEADER_IVF_RANGE = os.path.join(_ROOT, "include", "mips_hip_ivf_range.h")  # range search over the probed lists of an IVF index
 HEADER_WRITE = os.path.join(_ROOT, "include", "mips_hip_write.h")  # stored rows overwritten in place by id (flat and IVF index)
+HEADER_IVF_SHARDED = os.path.join(_ROOT, "include", "mips_hip_ivf_sharded.h")  # the IVF search cut at its merge, for row shards
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -47,7 +48,8 @@ _lib = None
 
 
 def _sources():
-    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE, HEADER_WRITE]
+    out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE, HEADER_WRITE,
+           HEADER_IVF_SHARDED]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -195,7 +197,12 @@ def _bind(lib):
         "mips_index_update": (i32, [vp, vp, i64, i64, vp, i32, i32, vp, vp]),
         "mips_ivf_update": (i32, [vp, vp, i64, i64, vp, i32, i32, vp, vp]),
     }
-    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range, **sig_write}.items():
+    sig_ivf_sharded = {  # include/mips_hip_ivf_sharded.h
+        "mips_ivf_search_part": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp, i64, i64, vp, i32, vp]),
+        "mips_ivf_merge_parts": (i32, [vp, i32, i64, i32, vp, vp, vp, i32, vp]),
+    }
+    for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range, **sig_write,
+                              **sig_ivf_sharded}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -225,6 +232,7 @@ EXPORTS_IVF = ("mips_ivf_create", "mips_ivf_destroy", "mips_ivf_flat", "mips_ivf
                "mips_ivf_search", "mips_ivf_search_sel", "mips_ivf_search_grp", "mips_ivf_search_wide", "mips_ivf_search_wide_grp")  # mips_hip_ivf.h
 EXPORTS_IVF_RANGE = ("mips_ivf_range_search", "mips_ivf_range_search_grp")  # include/mips_hip_ivf_range.h, likewise
 EXPORTS_WRITE = ("mips_index_update", "mips_ivf_update")  # include/mips_hip_write.h, likewise
+EXPORTS_IVF_SHARDED = ("mips_ivf_search_part", "mips_ivf_merge_parts")  # include/mips_hip_ivf_sharded.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:

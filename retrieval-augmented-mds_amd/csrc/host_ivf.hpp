@@ -13,7 +13,8 @@ struct IvfSearchScratch {
     Buffer ps, pi;            // the probe [ns][p]: scores, list numbers (int64)
     Buffer qbuf, qf32, qbias; // staged queries as the flat index stages them (+ B_q of an SQ8 index)
     Buffer parts;             // [p * S][ns][k][2] sorted partial lists
-    Buffer out_s, out_i;      // [nq][k] of a host-output call
+    Buffer out_s, out_i;      // [nq][k] of a host-output call, and the merged lists of a part search before they are packed
+    Buffer packed;            // [nq][k][2] of a host-output part search (mips_ivf_search_part)
     Buffer sel, qlab;         // a host bitmap and host query labels of a filtered call (mips_ivf_search_sel / _grp)
 };
 
@@ -177,12 +178,20 @@ void ivf_launch_wide_scan(bool filtered, bool f32x, bool sq8, unsigned grid, hip
     else mips::ivf_list_scan_wide_kernel<mips::ElemBF16, mips::ElemBF16, false, KP><<<grid, threads, 0, st>>>(a);
 }
 
+// What mips_ivf_search_part (host_ivf_sharded.hpp) takes in the place of out_scores / out_idx: the payload [nq][k][2] and, of an SQ8
+// index, B_q [nq] -- host or device as the flags say.
+struct IvfPartOut {
+    int64_t* packed;
+    double* bias;
+};
+
 // mips_ivf_search (sel_bits == nullptr and q_labels == nullptr: the unfiltered launch sequence, nothing else is touched) and
 // mips_ivf_search_sel / _grp: the same sequence with the filtered instance of the list scan.  wide (mips_ivf_search_wide / _grp):
-// k up to MIPS_MAX_K_WIDE; the same sequence again, with the wide list scan as launch 3 when k > MIPS_MAX_K
+// k up to MIPS_MAX_K_WIDE; the same sequence again, with the wide list scan as launch 3 when k > MIPS_MAX_K.  part (wide only): the
+// search cut behind its merge -- ivf_part_pack_kernel in the place of ivf_finish_kernel, B_q handed to the caller, nothing kept
 int ivf_search_impl(const char* who, bool wide, mips_ivf* v, const void* q, int q_dtype, int64_t nq, int k, int64_t nprobe, float* out_scores, int64_t* out_idx,
                     int64_t idx_offset, int flags, const uint8_t* sel_bits, int64_t sel_nbits, int64_t sel_bit0, const int32_t* q_labels, int grp_mode,
-                    void* hip_stream) {
+                    void* hip_stream, const IvfPartOut* part = nullptr) {
     int rc = ivf_check(who, v);
     if (rc) return rc;
     if (mips_ivf_is_trained(v) != 1) return fail(MIPS_E_INVALID, "%s: the IVF index is not trained (mips_ivf_train / mips_ivf_set_centroids)", who);
@@ -201,7 +210,7 @@ int ivf_search_impl(const char* who, bool wide, mips_ivf* v, const void* q, int 
     Selector sel;
     if (filtered && (rc = make_selector(who, ix, flags, sel_bits, sel_nbits, sel_bit0, q_labels, grp_mode, sel))) return rc;
     if (nq == 0) return MIPS_OK;
-    if (!out_scores || !out_idx) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
+    if (part ? !part->packed || (ix->sq8 && !part->bias) : !out_scores || !out_idx) return fail(MIPS_E_INVALID, "%s: NULL buffer", who);
     const bool q_dev = (flags & MIPS_Q_DEVICE) != 0, out_dev = (flags & MIPS_OUT_DEVICE) != 0;
     const bool f32x = ix->plane > 0;
     const int ld = f32x ? ix->plane : ix->ld; // elements per canonical row and per staged query
@@ -214,11 +223,24 @@ int ivf_search_impl(const char* who, bool wide, mips_ivf* v, const void* q, int 
     IvfSearchScratch& ss = v->ss;
     float* d_s = out_scores;
     int64_t* d_i = out_idx;
-    if (!out_dev) {
+    if (!out_dev || part) {
         if ((rc = ss.out_s.ensure((size_t)nq * k * sizeof(float)))) return rc;
         if ((rc = ss.out_i.ensure((size_t)nq * k * sizeof(int64_t)))) return rc;
         d_s = (float*)ss.out_s.p;
         d_i = (int64_t*)ss.out_i.p;
+    }
+    // a part search: the payload and B_q of ALL the queries go to the caller's device buffers, or to scratch on their way to the host
+    int64_t* d_pk = nullptr;
+    double* d_b = nullptr;
+    if (part) {
+        d_pk = part->packed;
+        d_b = part->bias;
+        if (!out_dev) {
+            if ((rc = ss.packed.ensure((size_t)ivf::packed_words(nq, k) * sizeof(int64_t)))) return rc;
+            d_pk = (int64_t*)ss.packed.p;
+            if (ix->sq8 && (rc = ss.qbias.ensure((size_t)nq * sizeof(double)))) return rc;
+            d_b = (double*)ss.qbias.p;
+        }
     }
     // a host bitmap (the bytes that hold bits sel_bit0 .. sel_bit0 + ntotal - 1) and host query labels travel by the stream's
     // asynchronous copy into the search's scratch; device ones are read where they are
@@ -251,8 +273,9 @@ int ivf_search_impl(const char* who, bool wide, mips_ivf* v, const void* q, int 
             if ((rc = ss.qf32.ensure((size_t)ns * ix->plane * sizeof(float)))) return rc;
             rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, (float*)ss.qf32.p);
         } else {
-            if (ix->sq8 && (rc = ss.qbias.ensure((size_t)ns * sizeof(double)))) return rc;
-            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize, (double*)ss.qbias.p);
+            if (ix->sq8 && !part && (rc = ss.qbias.ensure((size_t)ns * sizeof(double)))) return rc;
+            rc = convert_into(ix, qs, ns, q_dtype, q_dev, (uint8_t*)ss.qbuf.p, st, nullptr, 0, nullptr, 0, ix->qsize,
+                              part ? (d_b ? d_b + s0 : nullptr) : (double*)ss.qbias.p);
         }
         if (rc) return rc;
         // 3. the list scan: one workgroup per (query, probed list, segment)
@@ -292,11 +315,24 @@ int ivf_search_impl(const char* who, bool wide, mips_ivf* v, const void* q, int 
         else if (ix->sq8) mips::ivf_list_scan_kernel<mips::ElemU8, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
         else mips::ivf_list_scan_kernel<mips::ElemBF16, mips::ElemBF16><<<grid, threads, 0, st>>>(a);
         HIP_TRY(hipGetLastError());
-        // 4. the merge of the sorted partials (score descending, row ascending, padding last), then S -> D and idx_offset
+        // 4. the merge of the sorted partials (score descending, row ascending, padding last), then S -> D and idx_offset -- or, of a
+        //    part search, the payload: the ranking score as it is, idx_offset added
         if ((rc = mips_merge_topk_sorted_packed(a.parts, ns, parts, k, MIPS_METRIC_IP, d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, v->device, st))) return rc;
-        mips::ivf_finish_kernel<<<grid_for(ns * k, 256), 256, 0, st>>>(d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, ix->sq8 ? (const double*)ss.qbias.p : nullptr, ns,
-                                                                      k, idx_offset);
+        if (part)
+            mips::ivf_part_pack_kernel<<<grid_for(ns * k, 256), 256, 0, st>>>(d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, ns, k, idx_offset,
+                                                                             d_pk + ivf::packed_words(s0, k));
+        else
+            mips::ivf_finish_kernel<<<grid_for(ns * k, 256), 256, 0, st>>>(d_s + (size_t)s0 * k, d_i + (size_t)s0 * k, ix->sq8 ? (const double*)ss.qbias.p : nullptr, ns,
+                                                                          k, idx_offset);
         HIP_TRY(hipGetLastError());
+    }
+    if (part) {
+        if (!out_dev) {
+            HIP_TRY(hipMemcpyAsync(part->packed, d_pk, (size_t)ivf::packed_words(nq, k) * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+            if (ix->sq8) HIP_TRY(hipMemcpyAsync(part->bias, d_b, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+        return MIPS_OK;
     }
     if (!out_dev) {
         HIP_TRY(hipMemcpyAsync(out_scores, d_s, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -24,6 +24,7 @@
 #include "../../include/mips_hip_sq8.h"
 #include "../../include/mips_hip_ivf.h"
 #include "../../include/mips_hip_ivf_range.h"
+#include "../../include/mips_hip_ivf_sharded.h"
 #include "../../include/mips_hip_write.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
@@ -47,6 +48,7 @@
 #include "ivf_search_kernels.hpp"
 #include "ivf_wide_kernels.hpp"
 #include "ivf_range_kernels.hpp"
+#include "ivf_sharded_kernels.hpp"
 #include "update_kernels.hpp"
 
 #include "search_report.hpp"
@@ -1113,3 +1115,4 @@ int mips_scan_timing(mips_index_t* ix, float* out_sum_ms, int* out_count, int re
 
 #include "host_ivf.hpp" // the IVF index (include/mips_hip_ivf.h): its own entry points, behind everything they call
 #include "host_ivf_range.hpp" // its range search (include/mips_hip_ivf_range.h)
+#include "host_ivf_sharded.hpp" // its search cut at the merge, for row shards (include/mips_hip_ivf_sharded.h)

@@ -4,7 +4,8 @@ Building and maintaining the file: deterministic k-means training, the list of e
 P(q) of a query, removal, reset, save / load.  Searching it: `search_probed` scores every row of the probed lists exactly and
 returns what `flat.search` would return if the other rows were deleted; `range_search_probed` returns every probed row above a
 per-query radius in CSR form (include/mips_hip_ivf_range.h); `flat` is the inner MipsIndex over the same rows and searches all of
-them.
+them.  `search_part` + `ivf_merge_parts` are the search cut behind its merge, for the row shards of a ShardedIvfIndex
+(include/mips_hip_ivf_sharded.h).
 
 All arithmetic happens in libmips_hip.so; this file moves pointers.  No CPU fallback.
 """
@@ -333,6 +334,44 @@ class IvfIndex:
         del keep, sel_keep, grp_keep
         return D, I
 
+    def search_part(self, x, k: int, nprobe: int | None = None, idx_offset: int = 0, selector=None, groups=None, group_mode: str = "exclude",
+                    sel_bit0: int = 0):
+        """The search of ONE PART of a row-sharded IVF index (include/mips_hip_ivf_sharded.h: mips_ivf_search_part): search_probed_wide
+        cut behind its merge.  -> (payload, bias): payload int64 [nq, k, 2] = {float32 bits of the RANKING score (an 'sq8' index: S, not
+        D), row + idx_offset}, padding {bits of -inf, -1}; bias float64 [nq] = B_q on an 'sq8' index, None otherwise.  ivf_merge_parts
+        over the payloads of all parts finishes the search.  Arguments and NumPy / CUDA forms as search_probed_wide; nothing of the
+        call stays in the index."""
+        nprobe = int(self.nprobe if nprobe is None else nprobe)
+        k = int(k)
+        if k > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"search_part: k = {k} exceeds MAX_K_WIDE = {_lib.MAX_K_WIDE}")
+        ptr, code, is_dev, nq, keep = self._rows(x, "search_part")
+        if selector is not None:
+            from .selector import Selector, is_id_list
+
+            if is_id_list(selector):
+                selector = Selector.from_ids(selector, int(sel_bit0) + self.ntotal, device=self.device)
+        sel_ptr, sel_nbits, sel_flag, sel_keep = self.flat._sel_args(selector, sel_bit0, "search_part")
+        grp_ptr, grp_mode, grp_flag, grp_keep = self.flat._grp_args(groups, group_mode, nq, "search_part")
+        sq8 = self.dtype == "sq8"
+        if is_dev:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            P = torch.empty((nq, max(k, 0), 2), dtype=torch.int64, device=dev)
+            B = torch.empty(nq, dtype=torch.float64, device=dev) if sq8 else None
+            pp, bp, flags = P.data_ptr(), (B.data_ptr() if sq8 else None), _lib.Q_DEVICE | _lib.OUT_DEVICE
+        else:
+            P = np.empty((nq, max(k, 0), 2), np.int64)
+            B = np.empty(nq, np.float64) if sq8 else None
+            pp, bp, flags = P.ctypes.data, (B.ctypes.data if sq8 else None), 0
+        with self._mutex:
+            _lib.check(self._lib.mips_ivf_search_part(self._h, ptr, code, nq, k, nprobe, pp, bp, int(idx_offset), flags | sel_flag | grp_flag,
+                                                      sel_ptr, sel_nbits, int(sel_bit0), grp_ptr, grp_mode, _stream_handle(self.device)),
+                       "mips_ivf_search_part")
+        del keep, sel_keep, grp_keep
+        return P, B
+
     # ------------------------------------------------------------------ range search over the probed lists
     def _range_radii(self, radius, nq: int):
         """-> (pointer, flag, keepalive): a CUDA float32 tensor [nq] is read where it is (MIPS_RADII_DEVICE); anything else becomes
@@ -479,3 +518,25 @@ class IvfIndex:
                 ix.flat.set_labels(np.fromfile(os.path.join(path, "labels.i32"), dtype="<i4"))
         ix.meta = meta
         return ix
+
+
+def ivf_merge_parts(gathered, parts: int, nq: int, k: int, bias=None):
+    """The merge of the gathered payloads of IvfIndex.search_part (include/mips_hip_ivf_sharded.h: mips_ivf_merge_parts): gathered is
+    a contiguous CUDA int64 tensor of parts * nq * k * 2 words, part p (lower global rows than part p + 1) first; bias a CUDA float64
+    tensor [nq] (any part's B_q: an 'sq8' index) or None.  -> (D float32 [nq, k], I int64 [nq, k]) on gathered's device,
+    stream-ordered; the order is fixed on the ranking scores and S becomes D = (float)((double)S + B_q) behind it."""
+    import torch
+
+    parts, nq, k = int(parts), int(nq), int(k)
+    if not (isinstance(gathered, torch.Tensor) and gathered.is_cuda and gathered.dtype == torch.int64 and gathered.is_contiguous()
+            and gathered.numel() == parts * nq * k * 2):
+        raise ValueError(f"ivf_merge_parts: gathered must be a contiguous CUDA int64 tensor of {parts} x {nq} x {k} x 2 words")
+    dev = gathered.device
+    if bias is not None and not (isinstance(bias, torch.Tensor) and bias.device == dev and bias.dtype == torch.float64 and bias.is_contiguous()
+                                 and bias.numel() == nq):
+        raise ValueError(f"ivf_merge_parts: bias must be a contiguous float64 tensor [{nq}] on {dev}")
+    D = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+    I = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().mips_ivf_merge_parts(gathered.data_ptr(), parts, nq, k, bias.data_ptr() if bias is not None else None, D.data_ptr(),
+                                                I.data_ptr(), dev.index, _stream_handle(dev.index)), "mips_ivf_merge_parts")
+    return D, I

@@ -69,6 +69,69 @@ def range_record_views(rec, nq: int, stride: int):
     return rec[:nq + 1], rec[nq + 1 + stride:].view(torch.float32)[:stride], rec[nq + 1:nq + 1 + stride]
 
 
+def range_record_fill(home, nq: int, stride: int, search_into=None, search_host=None):
+    """A shard's range-search hits as a record of `stride` entries on the device `home`: search_into(lims, D, I) searches straight
+    into the record's three views (the device step), or search_host() -> NumPy (lims, D, I) is copied into it (an injected step).
+    The lims are the true counts whatever the stride is; entries past it are dropped, as mips_range_search drops them."""
+    import torch
+
+    if search_into is not None:
+        rec = torch.empty(_lib.range_record_words(nq, stride), dtype=torch.int64, device=home)
+        search_into(*range_record_views(rec, nq, stride))
+        return rec
+    lims, D, I = search_host()
+    rec = torch.zeros(_lib.range_record_words(nq, stride), dtype=torch.int64)
+    v_lims, v_D, v_I = range_record_views(rec, nq, stride)
+    m = min(stride, len(I))
+    v_lims.copy_(torch.from_numpy(np.ascontiguousarray(lims, dtype=np.int64)))
+    v_D[:m].copy_(torch.from_numpy(np.ascontiguousarray(D[:m], dtype=np.float32)))
+    v_I[:m].copy_(torch.from_numpy(np.ascontiguousarray(I[:m], dtype=np.int64)))
+    return rec.to(home)
+
+
+def range_record_exchange(ix, q, nq: int, local_record, as_numpy: bool):
+    """The record protocol of a sharded range search, for any index `ix` with world, group, _range_stride_guess, _range_gather and
+    _range_merge: local_record(stride) -> this shard's record.  Every shard searches into a record of the guessed capacity, ONE
+    scalar all-reduce (MAX) of the shards' totals is read on the host -- the call's synchronisation --, a shard that found more than
+    its record holds repeats its search once with that maximum, every record is brought to that common size, ONE all-gather moves
+    the records and the merge lays the shards' segments end to end per query.  -> (lims, D, I): NumPy when as_numpy, else on q's
+    device."""
+    import torch
+    import torch.distributed as dist
+
+    from .index import range_merge_records
+
+    stride = int(ix._range_stride_guess(nq))
+    rec = local_record(stride)
+    # the shards' totals: one scalar all-reduce, read on the host -- the call's synchronisation
+    if dist.get_backend(ix.group) == "nccl":
+        total = rec[nq:nq + 1].clone()
+        dist.all_reduce(total, op=dist.ReduceOp.MAX, group=ix.group)
+        common, own = (int(v) for v in torch.cat((total, rec[nq:nq + 1])).tolist())
+    else:
+        total = rec[nq:nq + 1].to("cpu", copy=True)  # (a copy also of a host record: the all-reduce writes in place)
+        own = int(total.item())
+        dist.all_reduce(total, op=dist.ReduceOp.MAX, group=ix.group)
+        common = int(total.item())
+    if own > stride:  # the guess was too small HERE: once more, with room for the largest shard result
+        stride = common
+        rec = local_record(stride)
+    if stride != common:  # the record at the common size: the lims and the `own` entries that count
+        fit = torch.empty(_lib.range_record_words(nq, common), dtype=torch.int64, device=rec.device)
+        for dst, src, n in zip(range_record_views(fit, nq, common), range_record_views(rec, nq, stride), (nq + 1, own, own)):
+            dst[:n].copy_(src[:n])
+        rec = fit
+    arrived, gathered = ix._range_gather(rec)
+    if ix._range_merge is None:
+        cap = int(arrived.view(ix.world, -1)[:, nq].sum().item())  # (on the host already under gloo)
+        out = range_merge_records(gathered, ix.world, nq, common, cap)
+    else:
+        out = ix._range_merge(arrived.cpu().numpy(), ix.world, nq, common)
+    if as_numpy:
+        return tuple(t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in out)
+    return tuple(t if isinstance(t, torch.Tensor) and t.device == q.device else torch.as_tensor(t).to(q.device) for t in out)
+
+
 class ShardedMipsIndex:
     """One logical exact index, row-sharded across the ranks of a torch.distributed group.
 
@@ -541,19 +604,9 @@ class ShardedMipsIndex:
 
         home = self._range_home()
         if self._local_range_search is None:
-            rec = torch.empty(_lib.range_record_words(nq, stride), dtype=torch.int64, device=home)
-            lims, D, I = range_record_views(rec, nq, stride)
-            self.local.range_search_into(q, r, lims, D, I, idx_offset=self.lo, **kw)
-            return rec
+            return range_record_fill(home, nq, stride, search_into=lambda lims, D, I: self.local.range_search_into(q, r, lims, D, I, idx_offset=self.lo, **kw))
         hq = q.detach().cpu().numpy() if isinstance(q, torch.Tensor) else q
-        lims, D, I = self._local_range_search(hq, r, self.lo, **kw)
-        rec = torch.zeros(_lib.range_record_words(nq, stride), dtype=torch.int64)
-        v_lims, v_D, v_I = range_record_views(rec, nq, stride)
-        m = min(stride, len(I))
-        v_lims.copy_(torch.from_numpy(np.ascontiguousarray(lims, dtype=np.int64)))
-        v_D[:m].copy_(torch.from_numpy(np.ascontiguousarray(D[:m], dtype=np.float32)))
-        v_I[:m].copy_(torch.from_numpy(np.ascontiguousarray(I[:m], dtype=np.int64)))
-        return rec.to(home)
+        return range_record_fill(home, nq, stride, search_host=lambda: self._local_range_search(hq, r, self.lo, **kw))
 
     def _range_gather(self, rec):
         """The ONE collective of the range calls: this rank's record in, the records end to end out -- as they arrived (on the
@@ -590,36 +643,7 @@ class ShardedMipsIndex:
             return self._local_range_search(q.detach().cpu().numpy() if not as_numpy else q, radius, self.lo, **kw)
         nq = int(q.shape[0])
         r = MipsIndex._radii(radius, nq)
-        stride = int(self._range_stride_guess(nq))
-        rec = self._range_local_record(q, r, nq, stride, kw)
-        # the shards' totals: one scalar all-reduce, read on the host -- the call's synchronisation
-        if dist.get_backend(self.group) == "nccl":
-            total = rec[nq:nq + 1].clone()
-            dist.all_reduce(total, op=dist.ReduceOp.MAX, group=self.group)
-            common, own = (int(v) for v in torch.cat((total, rec[nq:nq + 1])).tolist())
-        else:
-            total = rec[nq:nq + 1].to("cpu", copy=True)  # (a copy also of a host record: the all-reduce writes in place)
-            own = int(total.item())
-            dist.all_reduce(total, op=dist.ReduceOp.MAX, group=self.group)
-            common = int(total.item())
-        if own > stride:  # the guess was too small HERE: once more, with room for the largest shard result
-            stride = common
-            rec = self._range_local_record(q, r, nq, stride, kw)
-        if stride != common:  # the record at the common size: the lims and the `own` entries that count
-            fit = torch.empty(_lib.range_record_words(nq, common), dtype=torch.int64, device=rec.device)
-            for dst, src, n in zip(range_record_views(fit, nq, common), range_record_views(rec, nq, stride), (nq + 1, own, own)):
-                dst[:n].copy_(src[:n])
-            rec = fit
-        arrived, gathered = self._range_gather(rec)
-        if self._range_merge is None:
-            cap = int(arrived.view(self.world, -1)[:, nq].sum().item())  # (on the host already under gloo)
-            lims, D, I = range_merge_records(gathered, self.world, nq, common, cap)
-        else:
-            lims, D, I = self._range_merge(arrived.cpu().numpy(), self.world, nq, common)
-        out = (lims, D, I)
-        if as_numpy:
-            return tuple(t.cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t) for t in out)
-        return tuple(t if isinstance(t, torch.Tensor) and t.device == q.device else torch.as_tensor(t).to(q.device) for t in out)
+        return range_record_exchange(self, q, nq, lambda stride: self._range_local_record(q, r, nq, stride, kw), as_numpy)
 
     def range_search_into(self, q, radius, lims, D, I, part_cap: int, idx_offset: int = 0, force_ip: bool = False, selector=None,
                           groups=None, group_mode: str = "exclude") -> None:

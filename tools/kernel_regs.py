@@ -1,6 +1,7 @@
 """Register / spill / scratch / LDS figures of every gfx950 kernel in the built library (no GPU needed): extracts the code
 object from libmips_hip.so's .hip_fatbin and reads its note records.
-    python tools/kernel_regs.py [substring ...]      # only kernels whose demangled name contains one of the substrings"""
+    python tools/kernel_regs.py [substring ...]      # only kernels whose demangled name contains one of the substrings
+    python tools/kernel_regs.py --lib PATH [...]     # another build of the library ("" as the substring lists every kernel)"""
 import os
 import re
 import subprocess
@@ -31,8 +32,12 @@ def kernels(lib=os.path.join(ROOT, "retrieval-augmented-mds_amd", "lib", "libmip
 
 
 if __name__ == "__main__":
-    ks = kernels()
-    want = sys.argv[1:]
+    args = sys.argv[1:]
+    lib = args.pop(args.index("--lib") + 1) if "--lib" in args else None
+    if lib:
+        args.remove("--lib")
+    ks = kernels(lib) if lib else kernels()
+    want = args
     bad = 0
     for k in ks:
         flag = k["spill"] or k["scratch"]
