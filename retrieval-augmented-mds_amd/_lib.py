@@ -27,6 +27,7 @@ HEADER_IVF = os.path.join(_ROOT, "include", "mips_hip_ivf.h")  # the IVF index: 
 HEADER_IVF_RANGE = os.path.join(_ROOT, "include", "mips_hip_ivf_range.h")  # range search over the probed lists of an IVF index
 HEADER_WRITE = os.path.join(_ROOT, "include", "mips_hip_write.h")  # stored rows overwritten in place by id (flat and IVF index)
 HEADER_IVF_SHARDED = os.path.join(_ROOT, "include", "mips_hip_ivf_sharded.h")  # the IVF search cut at its merge, for row shards
+HEADER_PQ = os.path.join(_ROOT, "include", "mips_hip_pq.h")  # the product-quantised index: M one-byte codes per row, ADC search
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -49,7 +50,7 @@ _lib = None
 
 def _sources():
     out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE, HEADER_WRITE,
-           HEADER_IVF_SHARDED]
+           HEADER_IVF_SHARDED, HEADER_PQ]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -201,8 +202,26 @@ def _bind(lib):
         "mips_ivf_search_part": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp, i64, i64, vp, i32, vp]),
         "mips_ivf_merge_parts": (i32, [vp, i32, i64, i32, vp, vp, vp, i32, vp]),
     }
+    sig_pq = {  # include/mips_hip_pq.h
+        "mips_pq_create": (i32, [c.POINTER(vp), i32, i64, i64, i32, i32]),
+        "mips_pq_destroy": (i32, [vp]),
+        "mips_pq_train": (i32, [vp, vp, i64, i32, i32, vp]),
+        "mips_pq_is_trained": (i32, [vp]),
+        "mips_pq_set_codebook": (i32, [vp, vp]),
+        "mips_pq_get_codebook": (i32, [vp, vp]),
+        "mips_pq_add": (i32, [vp, vp, i64, i32, i32, vp]),
+        "mips_pq_add_codes": (i32, [vp, vp, i64, i32, vp]),
+        "mips_pq_read_codes": (i32, [vp, i64, i64, vp, vp]),
+        "mips_pq_search": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp]),
+        "mips_pq_reconstruct": (i32, [vp, vp, i64, i64, vp, i32, i64, i32, vp]),
+        "mips_pq_score_subset": (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i32, vp]),
+        "mips_pq_reset": (i32, [vp]),
+        "mips_pq_set_param": (i32, [vp, c.c_char_p, i64]),
+        "mips_pq_ntotal": (i64, [vp]),
+        "mips_pq_m": (i64, [vp]),
+    }
     for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range, **sig_write,
-                              **sig_ivf_sharded}.items():
+                              **sig_ivf_sharded, **sig_pq}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -233,6 +252,9 @@ EXPORTS_IVF = ("mips_ivf_create", "mips_ivf_destroy", "mips_ivf_flat", "mips_ivf
 EXPORTS_IVF_RANGE = ("mips_ivf_range_search", "mips_ivf_range_search_grp")  # include/mips_hip_ivf_range.h, likewise
 EXPORTS_WRITE = ("mips_index_update", "mips_ivf_update")  # include/mips_hip_write.h, likewise
 EXPORTS_IVF_SHARDED = ("mips_ivf_search_part", "mips_ivf_merge_parts")  # include/mips_hip_ivf_sharded.h, likewise
+EXPORTS_PQ = ("mips_pq_create", "mips_pq_destroy", "mips_pq_train", "mips_pq_is_trained", "mips_pq_set_codebook", "mips_pq_get_codebook",
+              "mips_pq_add", "mips_pq_add_codes", "mips_pq_read_codes", "mips_pq_search", "mips_pq_reconstruct", "mips_pq_score_subset",
+              "mips_pq_reset", "mips_pq_set_param", "mips_pq_ntotal", "mips_pq_m")  # include/mips_hip_pq.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:
