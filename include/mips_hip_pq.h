@@ -29,7 +29,7 @@
  *   score_subset     D(q_j, id) by the text above: scoring a search's rows reproduces its scores bit for bit
  * Refused: MIPS_METRIC_L2, nbits != 8, M > 128 (MIPS_E_UNSUPPORTED), d > 1024 (MIPS_E_UNSUPPORTED), M < 1 or d % M != 0
  * (MIPS_E_INVALID).  Not served at all: k > MIPS_MAX_K, range search, selectors and groups, removal and update by id, sharding,
- * IVF over PQ codes, OPQ.
+ * OPQ.  IVF over PQ codes is an index of its own: mips_hip_ivfpq.h.
  */
 #ifndef MIPS_HIP_PQ_H
 #define MIPS_HIP_PQ_H

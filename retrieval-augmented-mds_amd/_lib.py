@@ -28,6 +28,7 @@ HEADER_IVF_RANGE = os.path.join(_ROOT, "include", "mips_hip_ivf_range.h")  # ran
 HEADER_WRITE = os.path.join(_ROOT, "include", "mips_hip_write.h")  # stored rows overwritten in place by id (flat and IVF index)
 HEADER_IVF_SHARDED = os.path.join(_ROOT, "include", "mips_hip_ivf_sharded.h")  # the IVF search cut at its merge, for row shards
 HEADER_PQ = os.path.join(_ROOT, "include", "mips_hip_pq.h")  # the product-quantised index: M one-byte codes per row, ADC search
+HEADER_IVFPQ = os.path.join(_ROOT, "include", "mips_hip_ivfpq.h")  # the IVF index over PQ codes: lists, residual codes, ADC list scan
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -50,7 +51,7 @@ _lib = None
 
 def _sources():
     out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE, HEADER_WRITE,
-           HEADER_IVF_SHARDED, HEADER_PQ]
+           HEADER_IVF_SHARDED, HEADER_PQ, HEADER_IVFPQ]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -220,8 +221,32 @@ def _bind(lib):
         "mips_pq_ntotal": (i64, [vp]),
         "mips_pq_m": (i64, [vp]),
     }
+    sig_ivfpq = {  # include/mips_hip_ivfpq.h
+        "mips_ivfpq_create": (i32, [c.POINTER(vp), i32, i64, i64, i64, i32, i32, i32]),
+        "mips_ivfpq_destroy": (i32, [vp]),
+        "mips_ivfpq_train": (i32, [vp, vp, i64, i32, i32, vp]),
+        "mips_ivfpq_is_trained": (i32, [vp]),
+        "mips_ivfpq_set_centroids": (i32, [vp, vp]),
+        "mips_ivfpq_get_centroids": (i32, [vp, vp]),
+        "mips_ivfpq_set_codebook": (i32, [vp, vp]),
+        "mips_ivfpq_get_codebook": (i32, [vp, vp]),
+        "mips_ivfpq_add": (i32, [vp, vp, i64, i32, i32, vp]),
+        "mips_ivfpq_add_codes": (i32, [vp, vp, vp, i64, i32, vp]),
+        "mips_ivfpq_read_codes": (i32, [vp, i64, i64, vp, vp]),
+        "mips_ivfpq_read_assign": (i32, [vp, i64, i64, vp, vp]),
+        "mips_ivfpq_list_sizes": (i32, [vp, vp, vp]),
+        "mips_ivfpq_probe": (i32, [vp, vp, i32, i64, i64, vp, vp, i32, vp]),
+        "mips_ivfpq_search": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp]),
+        "mips_ivfpq_reconstruct": (i32, [vp, vp, i64, i64, vp, i32, i64, i32, vp]),
+        "mips_ivfpq_score_subset": (i32, [vp, vp, i32, i64, vp, i32, vp, i64, i32, vp]),
+        "mips_ivfpq_reset": (i32, [vp]),
+        "mips_ivfpq_set_param": (i32, [vp, c.c_char_p, i64]),
+        "mips_ivfpq_ntotal": (i64, [vp]),
+        "mips_ivfpq_nlist": (i64, [vp]),
+        "mips_ivfpq_m": (i64, [vp]),
+    }
     for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range, **sig_write,
-                              **sig_ivf_sharded, **sig_pq}.items():
+                              **sig_ivf_sharded, **sig_pq, **sig_ivfpq}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -255,6 +280,11 @@ EXPORTS_IVF_SHARDED = ("mips_ivf_search_part", "mips_ivf_merge_parts")  # includ
 EXPORTS_PQ = ("mips_pq_create", "mips_pq_destroy", "mips_pq_train", "mips_pq_is_trained", "mips_pq_set_codebook", "mips_pq_get_codebook",
               "mips_pq_add", "mips_pq_add_codes", "mips_pq_read_codes", "mips_pq_search", "mips_pq_reconstruct", "mips_pq_score_subset",
               "mips_pq_reset", "mips_pq_set_param", "mips_pq_ntotal", "mips_pq_m")  # include/mips_hip_pq.h, likewise
+EXPORTS_IVFPQ = ("mips_ivfpq_create", "mips_ivfpq_destroy", "mips_ivfpq_train", "mips_ivfpq_is_trained", "mips_ivfpq_set_centroids",
+                 "mips_ivfpq_get_centroids", "mips_ivfpq_set_codebook", "mips_ivfpq_get_codebook", "mips_ivfpq_add", "mips_ivfpq_add_codes",
+                 "mips_ivfpq_read_codes", "mips_ivfpq_read_assign", "mips_ivfpq_list_sizes", "mips_ivfpq_probe", "mips_ivfpq_search",
+                 "mips_ivfpq_reconstruct", "mips_ivfpq_score_subset", "mips_ivfpq_reset", "mips_ivfpq_set_param", "mips_ivfpq_ntotal",
+                 "mips_ivfpq_nlist", "mips_ivfpq_m")  # include/mips_hip_ivfpq.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:

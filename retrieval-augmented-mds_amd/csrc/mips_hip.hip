@@ -27,6 +27,7 @@
 #include "../../include/mips_hip_ivf_sharded.h"
 #include "../../include/mips_hip_write.h"
 #include "../../include/mips_hip_pq.h"
+#include "../../include/mips_hip_ivfpq.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -52,6 +53,7 @@
 #include "ivf_sharded_kernels.hpp"
 #include "update_kernels.hpp"
 #include "pq_kernels.hpp"
+#include "ivfpq_kernels.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"
@@ -1119,3 +1121,4 @@ int mips_scan_timing(mips_index_t* ix, float* out_sum_ms, int* out_count, int re
 #include "host_ivf_range.hpp" // its range search (include/mips_hip_ivf_range.h)
 #include "host_ivf_sharded.hpp" // its search cut at the merge, for row shards (include/mips_hip_ivf_sharded.h)
 #include "host_pq.hpp" // the product-quantised index (include/mips_hip_pq.h): an object of its own
+#include "host_ivfpq.hpp" // the IVF index over PQ codes (include/mips_hip_ivfpq.h): lists of the one, codes and tables of the other

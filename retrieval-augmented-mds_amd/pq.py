@@ -3,7 +3,7 @@ sub-quantisers of 256 centroids, asymmetric-distance search through a per-query 
 
 Reached by name only: the factory strings ("PQ16", "IVF4096,PQ32"), Mips, KnowledgeBase and faiss_shim do not route here.  Inner
 product only, 8 bits per code, M <= 128, d <= 1024, k <= MAX_K; no range search, selectors, groups, remove_ids, update_rows,
-sharding, IVF over the codes or OPQ.  Large query batches are served but are not what the index is for: the scan costs
+sharding or OPQ; lists over the codes are IvfPqIndex (ivfpq.py).  Large query batches are served but are not what the index is for: the scan costs
 nq * ntotal * M table reads and shares nothing between queries.
 
 All arithmetic happens in libmips_hip.so; this file moves pointers.  No CPU fallback.
