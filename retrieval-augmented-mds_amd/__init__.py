@@ -15,6 +15,7 @@ from .index import (MipsIndex, cosine_rescore, filter_ignore, l2_normalize_, mer
 from .ivf import IvfIndex, ivf_merge_parts
 from .pq import PqIndex
 from .ivfpq import IvfPqIndex
+from .refine import RefinedIndex
 from .mips import (KnowledgeBase, Mips, MipsArgs, MipsModelOutput, augment_xb, augment_xq, get_phi,
                    in_batch_scores, inner_product, retriever_metrics)
 from .selector import Selector
@@ -26,5 +27,5 @@ __all__ = [
     "get_phi", "augment_xb", "augment_xq", "inner_product", "in_batch_scores", "retriever_metrics", "IDX_POISON",
     "l2_normalize_", "rows_max_sumsq", "merge_topk", "merge_topk_packed", "merge_topk_sorted_packed", "range_merge_records", "filter_ignore", "cosine_rescore", "synth_fill", "shard_bounds", "pack_topk",
     "unpack_gathered", "build", "METRIC_IP", "METRIC_L2", "MAX_K", "MAX_K_WIDE", "faiss_shim",
-    "LABEL_NONE", "shard_offsets", "ShardedIvfIndex", "ivf_merge_parts", "PqIndex", "IvfPqIndex",
+    "LABEL_NONE", "shard_offsets", "ShardedIvfIndex", "ivf_merge_parts", "PqIndex", "IvfPqIndex", "RefinedIndex",
 ]

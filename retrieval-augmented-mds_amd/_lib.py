@@ -29,6 +29,7 @@ HEADER_WRITE = os.path.join(_ROOT, "include", "mips_hip_write.h")  # stored rows
 HEADER_IVF_SHARDED = os.path.join(_ROOT, "include", "mips_hip_ivf_sharded.h")  # the IVF search cut at its merge, for row shards
 HEADER_PQ = os.path.join(_ROOT, "include", "mips_hip_pq.h")  # the product-quantised index: M one-byte codes per row, ADC search
 HEADER_IVFPQ = os.path.join(_ROOT, "include", "mips_hip_ivfpq.h")  # the IVF index over PQ codes: lists, residual codes, ADC list scan
+HEADER_REFINE = os.path.join(_ROOT, "include", "mips_hip_refine.h")  # candidate search on PQ codes (k <= 1024) and exact re-ranking
 ABI_VERSION = 1
 
 # constants of include/mips_hip.h
@@ -51,7 +52,7 @@ _lib = None
 
 def _sources():
     out = [HEADER, HEADER_SHARDED, HEADER_UPDATE, HEADER_ROWS, HEADER_HOOK, HEADER_SQ8, HEADER_IVF, HEADER_IVF_RANGE, HEADER_WRITE,
-           HEADER_IVF_SHARDED, HEADER_PQ, HEADER_IVFPQ]
+           HEADER_IVF_SHARDED, HEADER_PQ, HEADER_IVFPQ, HEADER_REFINE]
     for f in sorted(os.listdir(CSRC)):
         if f.endswith((".hip", ".hpp", ".h")):
             out.append(os.path.join(CSRC, f))
@@ -245,8 +246,13 @@ def _bind(lib):
         "mips_ivfpq_nlist": (i64, [vp]),
         "mips_ivfpq_m": (i64, [vp]),
     }
+    sig_refine = {  # include/mips_hip_refine.h
+        "mips_pq_search_candidates": (i32, [vp, vp, i32, i64, i32, vp, vp, i64, i32, vp]),
+        "mips_ivfpq_search_candidates": (i32, [vp, vp, i32, i64, i32, i64, vp, vp, i64, i32, vp]),
+        "mips_index_rerank": (i32, [vp, vp, i32, i64, vp, i32, i32, vp, vp, i64, i32, vp]),
+    }
     for name, (res, args) in {**sig, **sig_sharded, **sig_update, **sig_rows, **sig_hook, **sig_sq8, **sig_ivf, **sig_ivf_range, **sig_write,
-                              **sig_ivf_sharded, **sig_pq, **sig_ivfpq}.items():
+                              **sig_ivf_sharded, **sig_pq, **sig_ivfpq, **sig_refine}.items():
         fn = getattr(lib, name)  # AttributeError if the library lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
@@ -285,6 +291,7 @@ EXPORTS_IVFPQ = ("mips_ivfpq_create", "mips_ivfpq_destroy", "mips_ivfpq_train", 
                  "mips_ivfpq_read_codes", "mips_ivfpq_read_assign", "mips_ivfpq_list_sizes", "mips_ivfpq_probe", "mips_ivfpq_search",
                  "mips_ivfpq_reconstruct", "mips_ivfpq_score_subset", "mips_ivfpq_reset", "mips_ivfpq_set_param", "mips_ivfpq_ntotal",
                  "mips_ivfpq_nlist", "mips_ivfpq_m")  # include/mips_hip_ivfpq.h, likewise
+EXPORTS_REFINE = ("mips_pq_search_candidates", "mips_ivfpq_search_candidates", "mips_index_rerank")  # include/mips_hip_refine.h, likewise
 
 
 def range_record_words(nq: int, stride: int) -> int:

@@ -187,6 +187,8 @@ struct mips_index {
     int64_t opt_remove_window = 0;
     // rows by id (include/mips_hip_rows.h, host_rows.hpp): the device copy of host ids, and the device result of a host-output call
     Buffer row_ids, row_out;
+    // exact re-ranking (include/mips_hip_refine.h, host_refine.hpp): the candidates' scores, and host ids / host results on the device
+    Buffer rr_scores, rr_ids, rr_out_s, rr_out_i;
     // rows overwritten by id (include/mips_hip_write.h, host_update.hpp; host ids stage into row_ids, host rows into stage): one
     // int32 per row of `capacity`, -1 between calls (the position that writes the row while a call runs), and the call's count
     DeviceArray<int> upd_owner;

@@ -28,6 +28,7 @@
 #include "../../include/mips_hip_write.h"
 #include "../../include/mips_hip_pq.h"
 #include "../../include/mips_hip_ivfpq.h"
+#include "../../include/mips_hip_refine.h"
 #include "aux_kernels.hpp"
 #include "scan_kernel.hpp"
 #include "scan_kernel_v3.hpp"
@@ -54,6 +55,7 @@
 #include "update_kernels.hpp"
 #include "pq_kernels.hpp"
 #include "ivfpq_kernels.hpp"
+#include "refine_kernels.hpp"
 
 #include "search_report.hpp"
 #include "host_state.hpp"
@@ -1122,3 +1124,4 @@ int mips_scan_timing(mips_index_t* ix, float* out_sum_ms, int* out_count, int re
 #include "host_ivf_sharded.hpp" // its search cut at the merge, for row shards (include/mips_hip_ivf_sharded.h)
 #include "host_pq.hpp" // the product-quantised index (include/mips_hip_pq.h): an object of its own
 #include "host_ivfpq.hpp" // the IVF index over PQ codes (include/mips_hip_ivfpq.h): lists of the one, codes and tables of the other
+#include "host_refine.hpp" // the two-stage search on PQ codes (include/mips_hip_refine.h): candidates and exact re-ranking

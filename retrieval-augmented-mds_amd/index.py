@@ -498,6 +498,49 @@ class MipsIndex:
         del keep, ikeep
         return out
 
+    def rerank(self, x, ids, k: int, idx_offset: int = 0):
+        """(D, I) [nq, k]: the best k of the SET of valid ids in each query's row of ids int64 [nq, kc], 1 <= k <= kc <= MAX_K_WIDE,
+        scored exactly (mips_index_rerank; faiss IndexRefineFlat's second stage).  An id is valid iff 0 <= id - idx_offset < ntotal;
+        every other value, the -1 padding of a search among them, is no row (host ids too: nothing raises), and a repeated id
+        counts once.  D is the score compute_distance_subset reports -- compute_distance_subset(x, I) reproduces it bit for bit --
+        and an id whose score is a NaN is dropped.  Order: (D descending, id ascending), -1 / -inf padding; I carries the ids as
+        given.  Inner-product indexes; on 'sq8' the order is that of the reported D, which need not be the order in which search
+        ranks the integer sums.  x on the host -> NumPy; x a CUDA tensor -> CUDA tensors (host ids are copied over first), and
+        with CUDA ids nothing synchronises (graph-capturable in steady state)."""
+        import torch
+
+        k = int(k)
+        if self._metric != _lib.METRIC_IP:
+            raise NotImplementedError("rerank: an inner-product index only (the order is score descending)")
+        if self._sq8 and not self.is_trained:
+            raise RuntimeError("rerank: the 'sq8' index is not trained (train(x) first)")
+        ptr, code, is_dev, nq, keep = self._as_buffer(x, "search")
+        if is_dev and not (isinstance(ids, torch.Tensor) and ids.is_cuda):
+            ids = torch.as_tensor(np.asarray(ids.cpu() if isinstance(ids, torch.Tensor) else ids), dtype=torch.int64).to(f"cuda:{self.device}")
+        iptr, shape, ids_dev, ikeep = self._ids_arg(ids, "rerank")
+        if len(shape) != 2 or shape[0] != nq:
+            raise ValueError(f"rerank: expected ids [{nq}, kc], got {shape}")
+        kc = int(shape[1])
+        if kc > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"rerank: kc = {kc} exceeds MAX_K_WIDE = {_lib.MAX_K_WIDE}")
+        if not 1 <= k <= kc:
+            raise ValueError(f"rerank: 1 <= k <= kc = {kc}, got k = {k}")
+        flags = _lib.IDS_DEVICE if ids_dev else 0
+        if is_dev:
+            dev = f"cuda:{self.device}"
+            D = torch.empty((nq, k), dtype=torch.float32, device=dev)
+            I = torch.empty((nq, k), dtype=torch.int64, device=dev)
+            dp, ip, flags = D.data_ptr(), I.data_ptr(), flags | _lib.Q_DEVICE | _lib.OUT_DEVICE
+        else:
+            D = np.empty((nq, k), dtype=np.float32)
+            I = np.empty((nq, k), dtype=np.int64)
+            dp, ip = D.ctypes.data, I.ctypes.data
+        with self._mutex:
+            _lib.check(self._lib.mips_index_rerank(self._h, ptr, code, nq, iptr, kc, k, dp, ip, int(idx_offset), flags,
+                                                   _stream_handle(self.device)), "mips_index_rerank")
+        del keep, ikeep
+        return D, I
+
     def search_and_reconstruct(self, x, k: int, **kw):
         """faiss Index.search_and_reconstruct -> (D, I, R [nq, k, d] float32): route_search(x, k, **kw) -- selector, groups and
         force_ip as there, k > MAX_K goes to the wide search -- and the rows of I.  The rows of the -1 slots are NaN."""

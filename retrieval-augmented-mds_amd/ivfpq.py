@@ -3,8 +3,8 @@ lists and nprobe as in IvfIndex, M one-byte codes per row as in PqIndex, the cod
 centroid.  A search reads only the codes of the probed lists; the score of a row is the probe's score of its list plus the ADC sum.
 
 Reached by name only: the factory strings ("IVF4096,PQ32"), Mips, KnowledgeBase and faiss_shim do not route here.  Inner product
-only, 8 bits per code, M <= 128, d <= 1024, nlist <= 65536, min(nprobe, nlist) <= 1024, k <= MAX_K; no range search, selectors,
-groups, remove_ids, update_rows, sharding or OPQ.
+only, 8 bits per code, M <= 128, d <= 1024, nlist <= 65536, min(nprobe, nlist) <= 1024, search k <= MAX_K (search_candidates:
+k <= MAX_K_WIDE); no range search, selectors, groups, remove_ids, update_rows, sharding or OPQ.
 
 All arithmetic happens in libmips_hip.so; this file moves pointers.  No CPU fallback.
 """
@@ -245,7 +245,7 @@ class IvfPqIndex:
         k = int(k)
         nprobe = int(self.nprobe if nprobe is None else nprobe)
         if k > _lib.MAX_K:
-            raise NotImplementedError(f"IvfPqIndex.search: k = {k} exceeds MAX_K = {_lib.MAX_K} (a wide search over PQ codes is not served)")
+            raise NotImplementedError(f"IvfPqIndex.search: k = {k} exceeds MAX_K = {_lib.MAX_K} (search_candidates serves k <= MAX_K_WIDE on PQ codes)")
         if min(nprobe, self._nlist) > 1024:
             raise NotImplementedError(f"IvfPqIndex.search: min(nprobe, nlist) = {min(nprobe, self._nlist)} exceeds 1024")
         ptr, code, is_dev, nq, keep = self._rows(x, "search")
@@ -263,6 +263,35 @@ class IvfPqIndex:
         with self._mutex:
             _lib.check(self._lib.mips_ivfpq_search(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags, _stream_handle(self.device)),
                        "mips_ivfpq_search")
+        del keep
+        return D, I
+
+    def search_candidates(self, x, k: int, nprobe: int | None = None, idx_offset: int = 0):
+        """(D, I) [nq, k] for 1 <= k <= MAX_K_WIDE: the definition of search, unchanged -- every row of the probed lists scored, the
+        best k by (D descending, row ascending), -1 / -inf padding; the first k' columns are the result for k'.  k <= MAX_K issues
+        search's own launches.  The candidate generator in front of MipsIndex.rerank (RefinedIndex).  NumPy in gives
+        NumPy out; a CUDA tensor in gives CUDA tensors out, stream-ordered, never synchronising (graph-capturable in steady state)."""
+        k = int(k)
+        nprobe = int(self.nprobe if nprobe is None else nprobe)
+        if k > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"IvfPqIndex.search_candidates: k = {k} exceeds MAX_K_WIDE = {_lib.MAX_K_WIDE}")
+        if min(nprobe, self._nlist) > 1024:
+            raise NotImplementedError(f"IvfPqIndex.search_candidates: min(nprobe, nlist) = {min(nprobe, self._nlist)} exceeds 1024")
+        ptr, code, is_dev, nq, keep = self._rows(x, "search_candidates")
+        if is_dev:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            D = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+            I = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+            dp, ip, flags = D.data_ptr(), I.data_ptr(), _lib.Q_DEVICE | _lib.OUT_DEVICE
+        else:
+            D = np.empty((nq, max(k, 0)), np.float32)
+            I = np.empty((nq, max(k, 0)), np.int64)
+            dp, ip, flags = D.ctypes.data, I.ctypes.data, 0
+        with self._mutex:
+            _lib.check(self._lib.mips_ivfpq_search_candidates(self._h, ptr, code, nq, k, nprobe, dp, ip, int(idx_offset), flags,
+                                                              _stream_handle(self.device)), "mips_ivfpq_search_candidates")
         del keep
         return D, I
 
@@ -320,7 +349,8 @@ class IvfPqIndex:
         return out
 
     def _refused(self, *a, **kw):
-        raise NotImplementedError("IvfPqIndex serves search(x, k <= MAX_K, nprobe), probe, reconstruct* and compute_distance_subset; wide k, range "
+        raise NotImplementedError("IvfPqIndex serves search(x, k <= MAX_K, nprobe), search_candidates(x, k <= MAX_K_WIDE, nprobe), probe, reconstruct* and "
+                                  "compute_distance_subset; search_wide, range "
                                   "search, selectors, groups, remove_ids, update_rows and sharding are not served on PQ codes (DESIGN.md 4m)")
 
     search_wide = range_search = search_packed = search_fused = remove_ids = update_rows = search_probed_wide = range_search_probed = _refused

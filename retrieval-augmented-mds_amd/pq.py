@@ -2,8 +2,8 @@
 sub-quantisers of 256 centroids, asymmetric-distance search through a per-query lookup table.
 
 Reached by name only: the factory strings ("PQ16", "IVF4096,PQ32"), Mips, KnowledgeBase and faiss_shim do not route here.  Inner
-product only, 8 bits per code, M <= 128, d <= 1024, k <= MAX_K; no range search, selectors, groups, remove_ids, update_rows,
-sharding or OPQ; lists over the codes are IvfPqIndex (ivfpq.py).  Large query batches are served but are not what the index is for: the scan costs
+product only, 8 bits per code, M <= 128, d <= 1024, search k <= MAX_K (search_candidates: k <= MAX_K_WIDE); no range
+search, selectors, groups, remove_ids, update_rows, sharding or OPQ; lists over the codes are IvfPqIndex (ivfpq.py).  Large query batches are served but are not what the index is for: the scan costs
 nq * ntotal * M table reads and shares nothing between queries.
 
 All arithmetic happens in libmips_hip.so; this file moves pointers.  No CPU fallback.
@@ -212,7 +212,7 @@ class PqIndex:
         stream-ordered, never synchronising (graph-capturable in steady state)."""
         k = int(k)
         if k > _lib.MAX_K:
-            raise NotImplementedError(f"PqIndex.search: k = {k} exceeds MAX_K = {_lib.MAX_K} (a wide search over PQ codes is not served)")
+            raise NotImplementedError(f"PqIndex.search: k = {k} exceeds MAX_K = {_lib.MAX_K} (search_candidates serves k <= MAX_K_WIDE on PQ codes)")
         ptr, code, is_dev, nq, keep = self._rows(x, "search")
         if is_dev:
             import torch
@@ -227,6 +227,32 @@ class PqIndex:
             dp, ip, flags = D.ctypes.data, I.ctypes.data, 0
         with self._mutex:
             _lib.check(self._lib.mips_pq_search(self._h, ptr, code, nq, k, dp, ip, int(idx_offset), flags, _stream_handle(self.device)), "mips_pq_search")
+        del keep
+        return D, I
+
+    def search_candidates(self, x, k: int, idx_offset: int = 0):
+        """(D, I) [nq, k] for 1 <= k <= MAX_K_WIDE: the definition of search, unchanged -- every row scored, the best k by (D
+        descending, row ascending), -1 / -inf padding; the first k' columns are the result for k'.  k <= MAX_K issues search's own
+        launches.  The candidate generator in front of MipsIndex.rerank (RefinedIndex).  NumPy in gives NumPy out; a
+        CUDA tensor in gives CUDA tensors out, stream-ordered, never synchronising (graph-capturable in steady state)."""
+        k = int(k)
+        if k > _lib.MAX_K_WIDE:
+            raise NotImplementedError(f"PqIndex.search_candidates: k = {k} exceeds MAX_K_WIDE = {_lib.MAX_K_WIDE}")
+        ptr, code, is_dev, nq, keep = self._rows(x, "search_candidates")
+        if is_dev:
+            import torch
+
+            dev = f"cuda:{self.device}"
+            D = torch.empty((nq, max(k, 0)), dtype=torch.float32, device=dev)
+            I = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+            dp, ip, flags = D.data_ptr(), I.data_ptr(), _lib.Q_DEVICE | _lib.OUT_DEVICE
+        else:
+            D = np.empty((nq, max(k, 0)), np.float32)
+            I = np.empty((nq, max(k, 0)), np.int64)
+            dp, ip, flags = D.ctypes.data, I.ctypes.data, 0
+        with self._mutex:
+            _lib.check(self._lib.mips_pq_search_candidates(self._h, ptr, code, nq, k, dp, ip, int(idx_offset), flags, _stream_handle(self.device)),
+                       "mips_pq_search_candidates")
         del keep
         return D, I
 
@@ -313,7 +339,8 @@ class PqIndex:
         return out
 
     def _refused(self, *a, **kw):
-        raise NotImplementedError("PqIndex serves search(x, k <= MAX_K), reconstruct* and compute_distance_subset; wide k, range search, selectors, "
+        raise NotImplementedError("PqIndex serves search(x, k <= MAX_K), search_candidates(x, k <= MAX_K_WIDE), reconstruct* and compute_distance_subset; "
+                                  "search_wide, range search, selectors, "
                                   "groups, remove_ids, update_rows and sharding are not served on PQ codes (DESIGN.md 4l)")
 
     search_wide = range_search = search_packed = search_fused = remove_ids = update_rows = _refused
